@@ -3,6 +3,7 @@
 and the achieved fraction of the HBM-read roofline (BASELINE.json `metric`, configs[2]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--kv L] [--model llama2-7b]
+                    [--dump-outputs DIR] [--full]
 
 One process per GPU (torchrun for N > 1).  Each rank holds an independent replica of the
 model with B decode streams (requests) and their fp16 KV caches in its own HBM: the path
@@ -12,9 +13,17 @@ each of the rank's B streams, replayed at position L-1 so every step reads exact
 slots (SURVEY 8(d) replay mode), greedy feedback on the device.  Synthetic random weights of
 the named architecture (no checkpoints are reachable); `data` says so.
 
-rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel:
-the W4 decode GEMM, live HIP-event timing on the engine stream) and `cpu_baseline` (the
-compiled reference's own CPU decode ops timed on this host, rank 0 / N=1 only).
+A plain run sets up, warms up, times the K steps and has rank 0 print ONE JSON line with the
+contract fields (`value`, `ms_per_step`, ...) and `step_roofline` (arithmetic on the timed steps).
+`--dump-outputs DIR` writes what the last timed step handed back (the token each stream decided,
+ti_engine_last_tokens) as DIR/tokens.npy (float32, [B]; DIR/tokens_rank<r>.npy per rank when N > 1);
+the weights, caches and first token are seeded, so two runs with the same arguments see the same inputs.
+
+`--full` adds everything that takes runs of its own: `calibration` (this GPU's HBM streamed in the
+same process), `roofline` / `attention_roofline` / `kernels` (dominant kernel: the W4 decode GEMM,
+in-step stamps and live HIP-event timing on the engine stream) and `cpu_baseline` (the compiled
+reference's own CPU decode ops timed on this host, rank 0 / N=1 only).  `--no-cpu-baseline`,
+`--kernel-reps` and `--stamp-steps` act only there.
 """
 from __future__ import annotations
 
@@ -215,9 +224,14 @@ def main() -> int:
     ap.add_argument("--kv", type=int, default=2048, help="KV length read per step")
     ap.add_argument("--model", default="llama2-7b", choices=sorted(MODELS))
     ap.add_argument("--seed", type=int, default=0x7157)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-reps", type=int, default=50)
-    ap.add_argument("--stamp-steps", type=int, default=20, help="stamped step replays for the in-step roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's decided tokens as DIR/tokens.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the HBM calibration, the per-kernel / in-step roofline and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--kernel-reps", type=int, default=50, help="(--full) launches per isolated kernel timing")
+    ap.add_argument("--stamp-steps", type=int, default=20,
+                    help="(--full) stamped step replays for the in-step roofline")
     ap.add_argument("--attn-splits", type=int, default=0, help="0 = the engine's policy")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only rehearsal of the replica launch / barrier / max-over-ranks path: no GPU, "
@@ -238,9 +252,10 @@ def main() -> int:
     import turboinfer_amd as T
 
     T.init(g.local_rank)
-    # same-run calibration of this box's HBM: every rate below can be read
-    # against it (1 GiB read by 2 workgroups per CU; device-to-device copy, read + write bytes)
-    hbm_read, hbm_copy = T.hbm_calibrate(1 << 30, 5)
+    if args.full:
+        # same-run calibration of the GPU's HBM: every rate below can be read
+        # against it (1 GiB read by 2 workgroups per CU; device-to-device copy, read + write bytes)
+        hbm_read, hbm_copy = T.hbm_calibrate(1 << 30, 5)
     m = MODELS[args.model]
     V, H, layers, nh, nkv, hd, I, bits, theta = m
     B, L = args.batch, args.kv
@@ -267,6 +282,67 @@ def main() -> int:
     value = tokens / dt
     ms_per_step = dt / args.steps * 1000.0
     sb, wb = step_bytes(m, B, L)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, B, g)
+
+    full = kernel_figures(T, e, args, m, sb) if args.full else None
+    e.close()
+
+    result = None
+    if g.rank == 0:
+        result = {
+            "metric": "decode tokens/s/GPU, Llama-7B-shape INT4 @2048 ctx; % HBM-read roofline",
+            "value": round(value, 3),
+            "unit": "tokens/s",
+            "n_gpus": g.world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "w4a16" if bits == 4 else ("w8a16" if bits == 8 else "f16"),
+            "data": "synthetic (seeded random weights of the named architecture, quantized per group of 128; "
+                    "synthetic fp16 KV cache)",
+            "config": {"workload": f"{args.model} INT{bits} g128 decode, {B} stream(s)/GPU, KV {L}, replay at pos {L - 1}",
+                       "model": args.model, "global_batch": B * g.world, "seq_len": L,
+                       "parallelism": f"replicas{g.world} (request-sharded, no collectives)"},
+            "step_roofline": {"bytes_per_step": int(sb), "weight_bytes": int(wb),
+                              "achieved_GBps": round(sb / (ms_per_step * 1e-3) / 1e9, 1),
+                              "frac": round(sb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              "roofline_tokens_per_s_per_gpu": round(B * HBM_PEAK_GBS * 1e9 / sb, 1)},
+        }
+        if args.full:
+            result.update(full)
+            result["calibration"] = {
+                "hbm_read_GBps": round(hbm_read, 1), "hbm_copy_GBps": round(hbm_copy, 1),
+                "note": "same run, this GPU: 1 GiB streamed once by 2 workgroups per CU (read) and "
+                        "hipMemcpyAsync device-to-device (read + write bytes); best of 5"}
+            if g.world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(m, L)
+            else:
+                result["cpu_baseline"] = None
+    g.barrier()
+    g.close()
+    if result is not None:
+        print(json.dumps(result))
+    return 0
+
+
+def dump_outputs(out_dir: str, e, B: int, g: "Group") -> None:
+    """What the replay path hands its caller after the last timed step: the token every stream
+    decided (ti_engine_last_tokens), as float32 [B] (token ids are below 2^24, so exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    name = "tokens.npy" if g.world == 1 else f"tokens_rank{g.rank}.npy"
+    np.save(os.path.join(out_dir, name), e.last_tokens(B).astype(np.float32))
+
+
+def kernel_figures(T, e, args, m, sb) -> dict:
+    """--full: the per-kernel and in-step roofline of the replay step (`roofline`,
+    `attention_roofline`, `kernels`), each from timing runs of its own after the timed steps."""
+    V, H, layers, nh, nkv, hd, I, bits, _ = m
+    B, L = args.batch, args.kv
 
     # Dominant kernel.  Live timing on the engine stream (ti_engine_time_kernel): the launches of
     # one class as the step runs them (same kernel, x mode and epilogue), cycling through the
@@ -359,30 +435,10 @@ def main() -> int:
            "isolated_frac": round(gemv_bytes / gemv_iso_us / 1e3 / HBM_PEAK_GBS, 4),
            "step_stamped_us": round(sum(d["period_us"] for d in stamps), 1)}
     achieved = gemv_bytes / gemv_us / 1e3   # GB/s
-    e.close()
 
     traffic, traffic_src = pmc_traffic(f"gemv_wq_kernel<{bits}>" if B == 1 else "gemm_family", args.model, B)
     att_traffic, _ = pmc_traffic("attn_split_kernel", args.model, B)
-    result = None
-    if g.rank == 0:
-        result = {
-            "metric": "decode tokens/s/GPU, Llama-7B-shape INT4 @2048 ctx; % HBM-read roofline",
-            "value": round(value, 3),
-            "unit": "tokens/s",
-            "n_gpus": g.world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "w4a16" if bits == 4 else ("w8a16" if bits == 8 else "f16"),
-            "data": "synthetic (seeded random weights of the named architecture, quantized per group of 128; "
-                    "synthetic fp16 KV cache)",
-            "config": {"workload": f"{args.model} INT{bits} g128 decode, {B} stream(s)/GPU, KV {L}, replay at pos {L - 1}",
-                       "model": args.model, "global_batch": B * g.world, "seq_len": L,
-                       "parallelism": f"replicas{g.world} (request-sharded, no collectives)"},
-            "roofline": dict({"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+    return {"roofline": dict({"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                               "traffic_source": traffic_src}, **dom),
             "attention_roofline": ({"bound": "hbm", "kernel": "attn_split_kernel", "achieved": per["attention"]["GBps"],
@@ -390,24 +446,7 @@ def main() -> int:
                                     "frac": round(per["attention"]["GBps"] / HBM_PEAK_GBS, 4), "traffic": att_traffic,
                                     "share_of_step_bytes": round(layers * att_bytes / sb, 4)} if not qa_on else
                                    {"fused_into": "qkv", "share_of_step_bytes": round(layers * att_bytes / sb, 4)}),
-            "calibration": {"hbm_read_GBps": round(hbm_read, 1), "hbm_copy_GBps": round(hbm_copy, 1),
-                            "note": "same run, this GPU: 1 GiB streamed once by 2 workgroups per CU (read) and "
-                                    "hipMemcpyAsync device-to-device (read + write bytes); best of 5"},
-            "step_roofline": {"bytes_per_step": int(sb), "weight_bytes": int(wb),
-                              "achieved_GBps": round(sb / (ms_per_step * 1e-3) / 1e9, 1),
-                              "frac": round(sb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                              "roofline_tokens_per_s_per_gpu": round(B * HBM_PEAK_GBS * 1e9 / sb, 1)},
-            "kernels": per,
-        }
-        if g.world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(m, L)
-        else:
-            result["cpu_baseline"] = None
-    g.barrier()
-    g.close()
-    if result is not None:
-        print(json.dumps(result))
-    return 0
+            "kernels": per}
 
 
 if __name__ == "__main__":

@@ -3,6 +3,6 @@ set -e
 for i in 1 2; do
   for v in d0 d10 d25 d60; do
     lib=turboinfer_amd/lib/exp/lib_$v.so; [ $v = d0 ] && lib=turboinfer_amd/lib/libturboinfer_amd.so
-    TI_LIB=$lib timeout -k 10 200 python bench.py --steps 512 --no-cpu-baseline --kernel-reps 200 > gpurun_out/ab_${v}_$i.log 2>&1
+    TI_LIB=$lib timeout -k 10 200 python bench.py --full --steps 512 --no-cpu-baseline --kernel-reps 200 > ${OUT_DIR:-bench_out}/ab_${v}_$i.log 2>&1
   done
 done

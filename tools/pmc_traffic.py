@@ -1,8 +1,8 @@
 """HBM traffic per launch from a rocprofv3 FETCH_SIZE pass (GPU-box output -> profiles/).
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc -o run -- \
-        python3 bench.py --steps 4 --warmup 2 --kernel-reps 4 --no-cpu-baseline [--model M --batch B]
-    python tools/pmc_traffic.py gpurun_out/pmc/run_counter_collection.csv profiles/r5_pmc_traffic.json \
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc -o run -- \
+        python3 bench.py --full --steps 4 --warmup 2 --kernel-reps 4 --no-cpu-baseline [--model M --batch B]
+    python tools/pmc_traffic.py OUT/pmc/run_counter_collection.csv profiles/r5_pmc_traffic.json \
         [--model llama2-7b --batch 1 --kv 2048]
 
 FETCH_SIZE is reported in KiB and, on gfx950, counts a wide coalesced streaming read at

@@ -9,8 +9,8 @@ launch, qkv_attn_kernel: DESIGN 4.19), labels the launches by their position in 
 K/V bytes added, as bench.py does; lm_head), and prints per class the average
 traced duration, the algorithmic bytes per launch (bench.py / ti_engine_time_kernel: packed
 weights + group scales + the fp16 input row) and GB/s, then the W4 GEMV family's
-sum(bytes) / sum(time) over a step's 4 x layers + 1 launches -- the quantity bench.py reports as
-`roofline.achieved` from its own HIP-event timing."""
+sum(bytes) / sum(time) over a step's 4 x layers + 1 launches -- the quantity `bench.py --full`
+reports as `roofline.achieved` from its own in-step timing."""
 from __future__ import annotations
 
 import argparse
