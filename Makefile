@@ -44,6 +44,11 @@ $(BUILD)/k_qkv_attn.o: turboinfer_amd/csrc/kernels/qkv_attn.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@
 
+# logprob: its lane merges are symmetric bit for bit only without fp contraction
+$(BUILD)/k_logprob.o: turboinfer_amd/csrc/kernels/logprob.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@
+
 $(BUILD)/k_%.o: turboinfer_amd/csrc/kernels/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@

@@ -125,6 +125,31 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int prompt_len, i
 int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new, int eos_token,
                     int chunk, int32_t* out_tokens, int32_t* out_len);
 
+/* Teacher-forced scoring of a token sequence on the device (InferenceEngine::compute_logprobs,
+ * inference_engine.cpp:873-954; Quantizer::validate_quantization_accuracy is built on it,
+ * quantization.cpp:548-549).  tokens[i] (host, [n]) is fed at position start_pos + i of stream slot
+ * `stream`, after whatever that slot's KV cache holds in [0, start_pos); out_logprob[i] (host, [n])
+ * is the log-probability of targets[i] under the model's output distribution after tokens[0..i],
+ * and out_top1[i] (host, [n], nullable) that distribution's argmax (lowest index on ties).
+ * targets (host, [n]): -1 = no target (0.0); NULL = tokens, the reference's own indexing (:934-942:
+ * position pos scores tokens[pos] with logits[pos]).  Perplexity passes targets[i] = tokens[i+1]
+ * and targets[n-1] = -1.
+ * The tokens run as prefill chunks (ti_engine_set_prefill's rows; when that is 0, the chunk
+ * ti_engine_serve uses), never as decode steps; after each chunk the final rms_norm + lm_head run on
+ * every row, TI_SCORE_ROWS rows at a time, into a logits scratch ([TI_SCORE_ROWS][vocab] fp32,
+ * allocated by the first call, outside what ti_engine_memory reports and outside the step graphs),
+ * and ti_logprob_rows (ti_hip.h) reduces each row to its two numbers.  One synchronisation and one
+ * copy of the n results at the end.  On return the slot's KV rows [start_pos, start_pos + n) hold
+ * what a prefill of the same tokens writes: ti_engine_generate or ti_engine_score with
+ * start_pos + n continues from there.  ti_engine_counters: prefill_chunks rises by the number of
+ * chunks, decode_steps does not move.
+ * TI_ERR_ARG, before anything is enqueued: null e / tokens / out_logprob, n < 1, stream outside
+ * [0, max_batch), start_pos < 0, start_pos + n > max_seq, a token outside [0, vocab), a target
+ * outside [-1, vocab).  TI_ERR_UNSUPPORTED: a compat engine. */
+#define TI_SCORE_ROWS 128
+int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int start_pos, const int32_t* targets,
+                    float* out_logprob, int32_t* out_top1);
+
 /* Prefill of ti_engine_generate's prompts (reference forward_pass, inference_engine.cpp:
  * 1429-1491): all but the last token of the shortest prompt are processed `rows` tokens at a
  * time as rows of the batched GEMMs and causal attention over the stream's own KV cache,

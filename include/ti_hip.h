@@ -24,6 +24,8 @@
  *   ti_softmax_f32        TensorEngine::softmax :925-1043 (same fast_exp_avx2 polynomial :262-302)
  *   ti_attention_f32      TensorEngine::multi_head_attention / attention_fast_incremental (fp32 op level)
  *   ti_argmax_f32         greedy InferenceEngine::sample_next_token (top_k = 1) :1554-1673
+ *   ti_logprob_rows       the per-position loop of InferenceEngine::compute_logprobs
+ *                         src/model/inference_engine.cpp:918-944 (max, sum of exp, picked logit)
  */
 #ifndef TI_HIP_H
 #define TI_HIP_H
@@ -459,6 +461,20 @@ int ti_attention_f32(const float* q, const float* k, const float* v, float* out,
                      int H, int heads, ti_stream_t s);
 /* out[r] = argmax_n x[r][n], lowest index on ties. */
 int ti_argmax_f32(const float* x, int32_t* out, int rows, int n, ti_stream_t s);
+
+/* ------------------------------------------------------- row log-softmax gather
+ * The per-position loop of InferenceEngine::compute_logprobs (inference_engine.cpp:918-944):
+ *   out_logprob[r] = logits[r*ld + targets[r]] - max_r - log(sum_v exp(logits[r*ld + v] - max_r))
+ * over v < vocab, one pass over each row (one 1024-thread workgroup per row, an online max / rescaled
+ * sum per lane, merged across the wave and through LDS).  logits, targets, out_logprob and out_top1
+ * are device pointers.  targets[r] = -1: no target, out_logprob[r] = 0; a target outside [-1, vocab)
+ * gives -20, the reference's LOGPROB_INVALID_TOKEN (:888, :935-938).  out_top1 (nullable) [rows]
+ * receives each row's argmax, lowest index on ties (the greedy argmax's rule).  Any vocab >= 1 and
+ * any ld >= vocab (16-byte loads from each row's first 16-byte boundary, scalar loads around them);
+ * rows < 1, vocab < 1, ld < vocab or a null pointer other than out_top1: TI_ERR_ARG, no launch.
+ * exp / log are the device's and the sum is a tree over the lanes (the reference sums in index order). */
+int ti_logprob_rows(const float* logits, int ld, int rows, int vocab, const int32_t* targets, float* out_logprob,
+                    int32_t* out_top1, ti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,7 @@ EXPORTED = [
     "ti_gemm_fold_partials", "ti_engine_set_stop", "ti_engine_counters",
     "ti_qkv_attn_partials", "ti_qkv_attn_part_o_elems", "ti_qkv_attn_part_ml_elems", "ti_engine_set_qkv_attn",
     "ti_qkv_attn_xchg_bytes", "ti_qkv_attn_supported", "ti_qkv_attn_error_offset",
+    "ti_logprob_rows", "ti_engine_score",
 ]
 
 _lib = None
@@ -201,6 +202,9 @@ def lib() -> C.CDLL:
             L.ti_qkv_attn_part_o_elems.restype = sz
             L.ti_qkv_attn_part_ml_elems.argtypes = [i32, i32, i32]
             L.ti_qkv_attn_part_ml_elems.restype = sz
+        if hasattr(L, "ti_engine_score"):   # (older TI_LIB builds in A/B runs lack it)
+            L.ti_logprob_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+            L.ti_engine_score.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]
@@ -350,6 +354,14 @@ def sample_token(logits, temperature=1.0, top_k=1, top_p=0.9, u=0.5):
     return t.value, lp.value
 
 
+def logprob_rows(logits: DeviceBuffer, ld: int, rows: int, vocab: int, targets: DeviceBuffer,
+                 out_logprob: DeviceBuffer, out_top1: DeviceBuffer | None = None, stream=None) -> None:
+    """ti_logprob_rows over device buffers: logits fp32 [rows][ld], targets int32 [rows] (-1 = none) ->
+    out_logprob fp32 [rows] = log_softmax(logits[r, :vocab])[targets[r]], out_top1 int32 [rows] = argmax."""
+    check(lib().ti_logprob_rows(logits.ptr, ld, rows, vocab, targets.ptr, out_logprob.ptr,
+                                None if out_top1 is None else out_top1.ptr, stream))
+
+
 class Engine:
     """ctypes wrapper over ti_engine (include/ti_engine.h)."""
 
@@ -409,6 +421,20 @@ class Engine:
         check(lib().ti_engine_generate(self.h, n, _ptr(P), _ptr(lens), stride, None if sp is None else _ptr(sp),
                                        max_new, _ptr(out), None if logits is None else _ptr(logits)))
         return (out, logits) if want_logits else out
+
+    def score(self, tokens, targets=None, stream=0, start_pos=0, want_top1=False):
+        """ti_engine_score: tokens fed at positions start_pos.. of slot `stream`; logprobs[i] = log p(targets[i])
+        after tokens[0..i] (targets None = tokens, -1 = no target -> 0.0); with want_top1 also each position's
+        argmax."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        tg = None if targets is None else np.ascontiguousarray(targets, np.int32).reshape(-1)
+        if tg is not None and tg.size != t.size:
+            raise TiError(f"score: {tg.size} targets for {t.size} tokens")
+        lp = np.zeros(t.size, np.float32)
+        top1 = np.zeros(t.size, np.int32) if want_top1 else None
+        check(lib().ti_engine_score(self.h, stream, _ptr(t), t.size, start_pos, None if tg is None else _ptr(tg),
+                                    _ptr(lp), None if top1 is None else _ptr(top1)))
+        return (lp, top1) if want_top1 else lp
 
     def generate_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, start_pos=None):
         """ti_engine_generate_sampled: tokens [n][max_new] and log-probs [n][max_new]."""

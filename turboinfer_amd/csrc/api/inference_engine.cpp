@@ -745,7 +745,19 @@ std::vector<GenerationResult> InferenceEngine::generate_beam_search(const std::v
   }
   return results;
 }
-std::vector<float> InferenceEngine::compute_logprobs(const std::vector<int>&) { off_path("compute_logprobs", "rank 1"); }
+// compute_logprobs (inference_engine.cpp:873-954): element i is log p(tokens[i]) under the logits of
+// position i (the reference's indexing, :934-942), scored on the device by ti_engine_score in stream
+// slot 0 from position 0.  Unlike the reference, a device error throws (check) instead of coming
+// back as a vector of -18.0f (LOGPROB_COMPUTATION_ERROR, :948-953): a sentinel would hide a GPU failure.
+std::vector<float> InferenceEngine::compute_logprobs(const std::vector<int>& tokens) {
+  validate_input_tokens(tokens);
+  InferenceEngineImpl& im = *impl_;
+  if (im.compat) off_path("compute_logprobs on the reference_compat plumbing model", "rank 1");
+  const std::vector<int32_t> t(tokens.begin(), tokens.end());
+  std::vector<float> lp(t.size());
+  check(ti_engine_score(im.eng, 0, t.data(), (int)t.size(), 0, nullptr, lp.data(), nullptr), "ti_engine_score");
+  return lp;
+}
 std::vector<int> InferenceEngine::encode(const std::string&) { off_path("encode", "-- the tokenizer"); }
 std::string InferenceEngine::decode(const std::vector<int>&) { off_path("decode", "-- the tokenizer"); }
 

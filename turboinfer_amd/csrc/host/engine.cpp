@@ -127,6 +127,11 @@ struct ti_engine {
   int32_t* pf_ones = nullptr;  // [pf_rows] 1
   int32_t* pf_zero = nullptr;  // [1] 0
   int32_t* pf_base = nullptr;  // [pf_rows] positions of the chunk's rows
+  // ti_engine_score (allocated by its first call; no step graph reads or writes them)
+  float* sc_logits = nullptr;    // [TI_SCORE_ROWS][vocab] logits of one block of chunk rows
+  int32_t* sc_targets = nullptr; // [max_seq]
+  float* sc_lp = nullptr;        // [max_seq]
+  int32_t* sc_top1 = nullptr;    // [max_seq]
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -1448,6 +1453,60 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
       if (slot_req[m] >= 0) slot_pos[m] += S;
     }
   }
+  return TI_OK;
+}
+
+// ------------------------------------------------------------------------------ scoring
+// InferenceEngine::compute_logprobs (inference_engine.cpp:873-954): the reference runs forward_pass
+// over the sequence and reduces every position's logits on the host (:918-944).  Here the tokens run
+// as prefill chunks into the slot's KV cache; after each chunk the final rms_norm + lm_head run on
+// its rows of e->h in blocks of TI_SCORE_ROWS into sc_logits, and ti_logprob_rows leaves one
+// log-probability (and argmax) per row on the device.  Nothing is read back until the end.
+int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int start_pos, const int32_t* targets,
+                    float* out_logprob, int32_t* out_top1) {
+  if (!e || !tokens || !out_logprob) return ti_set_error(TI_ERR_ARG, "ti_engine_score: null");
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_score: compat engine");
+  if (n < 1) return ti_set_error(TI_ERR_ARG, "ti_engine_score: n=%d", n);
+  if (stream < 0 || stream >= c.max_batch)
+    return ti_set_error(TI_ERR_ARG, "ti_engine_score: stream %d of %d", stream, c.max_batch);
+  if (start_pos < 0 || n > c.max_seq - start_pos)
+    return ti_set_error(TI_ERR_ARG, "ti_engine_score: start_pos %d + %d tokens, max_seq %d", start_pos, n, c.max_seq);
+  if (!targets) targets = tokens;
+  for (int i = 0; i < n; ++i) {
+    if (tokens[i] < 0 || tokens[i] >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "ti_engine_score: token %d at %d outside [0, vocab %d)", tokens[i], i, c.vocab);
+    if (targets[i] < -1 || targets[i] >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "ti_engine_score: target %d at %d outside [-1, vocab %d)", targets[i], i, c.vocab);
+  }
+  if (!e->sc_logits) {
+    TI_TRY(e->alloc_t(&e->sc_logits, (size_t)TI_SCORE_ROWS * c.vocab));
+    TI_TRY(e->alloc_t(&e->sc_targets, (size_t)c.max_seq));
+    TI_TRY(e->alloc_t(&e->sc_lp, (size_t)c.max_seq));
+    TI_TRY(e->alloc_t(&e->sc_top1, (size_t)c.max_seq));
+  }
+  TI_TRY(ensure_io(e, n, 1));
+  TI_TRY(ti_memcpy_h2d(e->in_tokens + (size_t)stream * e->in_cap, tokens, (size_t)n * 4, e->s));
+  TI_TRY(ti_memcpy_h2d(e->sc_targets, targets, (size_t)n * 4, e->s));
+  // (the chunk ti_engine_serve uses when prefill is off)
+  const int pf = e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16);
+  for (int t0 = 0; t0 < n; t0 += pf) {
+    const int rows = std::min(pf, n - t0);
+    TI_TRY(enqueue_prefill(e, stream, t0, rows, start_pos));
+    for (int r0 = 0; r0 < rows; r0 += TI_SCORE_ROWS) {
+      const int m = std::min(TI_SCORE_ROWS, rows - r0);
+      ti_epilogue el{};
+      el.kind = TI_EPI_STORE_F32;
+      el.ldo = c.vocab;
+      el.out = e->sc_logits;
+      TI_TRY(gemm_rows(e, e->lm, m, e->h + (size_t)r0 * c.hidden, TI_X_F32_RMSNORM, c.hidden, e->out_norm, el, 4, false));
+      TI_TRY(ti_logprob_rows(e->sc_logits, c.vocab, m, c.vocab, e->sc_targets + t0 + r0, e->sc_lp + t0 + r0,
+                             e->sc_top1 + t0 + r0, e->s));
+    }
+  }
+  TI_TRY(ti_memcpy_d2h(out_logprob, e->sc_lp, (size_t)n * 4, e->s));   // (synchronises the stream)
+  if (out_top1) TI_TRY(ti_memcpy_d2h(out_top1, e->sc_top1, (size_t)n * 4, e->s));
   return TI_OK;
 }
 
