@@ -9,8 +9,8 @@
  * (:244-279) -> KVCache::update_incremental (:78-160), plus greedy sample_next_token
  * (:1554-1673, top_k = 1) and the generate() loop (:734-802).
  *
- * One engine = one device + one HIP stream + B decode streams (requests) whose fp16 KV
- * caches live in that device's HBM.  Independent engines on different devices are
+ * One engine = one device + one HIP stream + B decode streams (requests) whose fp16 (or, with
+ * TI_BITS_KV8, e4m3) KV caches live in that device's HBM.  Independent engines on different devices are
  * independent replicas (no collectives).
  */
 #ifndef TI_ENGINE_H
@@ -29,7 +29,11 @@ typedef struct ti_engine_config {
   int32_t vocab, hidden, layers, heads, kv_heads, head_dim, inter;
   float rope_theta;        /* ModelMetadata::rope_theta (reference default 10000) */
   float eps;               /* rms_norm eps, reference default 1e-5 (tensor_engine.hpp:185) */
-  int32_t bits;            /* weight format: 4 (INT4 g128), 8 (INT8 g128), 16 (fp16) */
+  int32_t bits;            /* weight format: 4 (INT4 g128), 8 (INT8 g128), 16 (fp16); | TI_BITS_KV8
+                              (ti_hip.h): K / V kept as e4m3 bytes, half the cache memory -- the
+                              one-stream fused QKV + attention launch is then off and prompt
+                              chunks attend through the decode kernel; not with
+                              compat (TI_ERR_ARG) */
   int32_t max_seq;         /* KV slots per stream */
   int32_t max_batch;       /* decode streams held by the engine */
   int32_t compat;          /* 1 = reference_compat: placeholder embeddings, attention
@@ -68,6 +72,14 @@ int ti_engine_set_tensor_q1(ti_engine* e, int slot, int layer, const uint8_t* q,
 int ti_engine_synth(ti_engine* e, uint64_t seed, float norm_jitter);
 /* Fill KV slots [0, n) of `stream` (all layers) with seeded fp16 U(-1,1) (or_model_fill_kv). */
 int ti_engine_fill_kv(ti_engine* e, int stream, int n, uint64_t seed);
+
+/* (a TI_BITS_KV8 engine stores the e4m3 of exactly those fp16 values) */
+/* Copy rows [pos0, pos0 + n) of one stream slot's K (which = 0) or V (which = 1) cache of `layer` to
+ * the host as [kv_heads][n][head_dim] in the engine's own element type: fp16 bits (2 bytes), or e4m3
+ * bytes on a TI_BITS_KV8 engine.  For inspecting or persisting a slot; synchronises the engine's
+ * stream.  TI_ERR_ARG before any copy: null e / out, a compat engine, layer outside [0, layers),
+ * stream outside [0, max_batch), which not 0 / 1, pos0 < 0, n < 1, pos0 + n > max_seq. */
+int ti_engine_read_kv(ti_engine* e, int layer, int stream, int which, int pos0, int n, void* out);
 
 /* Greedy generation for n_streams independent requests, entirely on the device: every
  * stream starts at position start_pos[s] (NULL = 0), consumes its prompt one token per

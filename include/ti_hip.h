@@ -116,6 +116,12 @@ int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_src, int N_
  * (ti_wpack_scale_bytes counts both).  The kernels add (8 d + m) * (the block's sum of x) per
  * block.  Fused kernel only (more rows run in pieces); no tile GEMM, no packed rows. */
 #define TI_BITS_AFF 64
+/* 8-bit KV cache: a flag OR-ed into ti_engine_config.bits with any weight format (never a weight
+ * format itself: ti_wpack_* and ti_gemm_wq_a16 do not take it).  K / V are kept as OCP e4m3fn bytes
+ * without a scale: byte = round-to-nearest-even e4m3 of min(max(x, -448), 448), converted from the
+ * fp32 value the QKV epilogue holds; layout and strides unchanged in elements (ti_epilogue.kv_fp8,
+ * ti_attn_decode_f8). */
+#define TI_BITS_KV8 128
 /* q uint8 [K][N_src] (0..15), d and m fp16 [K/32][N_src]: weight(k, c) = d * q + m. */
 int ti_wpack_q1_host(const uint8_t* q, const uint16_t* d, const uint16_t* m, int K, int N_src, int N_total, int row_map,
                      int row_offset, void* tiles, uint16_t* scales);
@@ -137,10 +143,17 @@ int ti_fill_uniform_f32(uint64_t seed, uint32_t tensor_id, uint64_t n, float mul
  * n_tab fp16 cache base pointers (layer K / V); per cache, `rows` rows of row_elems elements
  * (pitch row_pitch) from element offset src_off to dst_off.  row_elems, row_pitch and the
  * offsets are multiples of 8. */
+/* An e4m3 cache (one byte per element) is passed as the same bytes counted in 2-byte units: its base
+ * pointers cast to uint16_t*, and src_off, dst_off, row_pitch and row_elems at half their element
+ * counts (each still a multiple of 8, i.e. whole 16-byte pieces). */
 int ti_kv_copy_slots(uint16_t* const* tab, int n_tab, int64_t src_off, int64_t dst_off, int rows, int64_t row_pitch,
                      int64_t row_elems, ti_stream_t s);
 int ti_fill_kv_uniform(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim, int max_seq,
                        uint16_t* dst, ti_stream_t s);
+/* The same fill into an e4m3 cache: each byte is the e4m3 (TI_BITS_KV8 rounding) of exactly the fp16
+ * value ti_fill_kv_uniform writes for the same seed. */
+int ti_fill_kv_uniform_f8(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim, int max_seq,
+                          uint8_t* dst, ti_stream_t s);
 
 /* ---------------------------------------------------- fused decode GEMM/GEMV
  * y[m][n] = sum_k xa[m][k] * W[k][n], m < M <= TI_GEMM_MAX_ROWS (see ti_gemm_max_rows), with
@@ -230,6 +243,10 @@ typedef struct ti_epilogue {
   void* splitk_ws;
   int64_t splitk_bytes;
   int32_t fold_packed;
+  /* TI_EPI_QKV_ROPE_KV: 1 = k_cache / v_cache point at e4m3 bytes (TI_BITS_KV8: one byte per element,
+   * the same layout and kv_stream_stride in elements); k and v are converted from the epilogue's fp32
+   * values, q is unchanged */
+  int32_t kv_fp8;
 } ti_epilogue;
 #define TI_FOLD_SS_ROWS 64
 #define TI_SPLITK_TICKET_BYTES (256 * 1024)
@@ -317,6 +334,21 @@ int ti_attn_decode_partials(const float* q, const uint16_t* k_cache, const uint1
                             int64_t kv_stream_stride, int max_seq, const int32_t* pos, int M, int heads,
                             int kv_heads, int head_dim, int splits, uint16_t* part_o, float* part_ml,
                             ti_stream_t s);
+/* The three entry points over an e4m3 cache (TI_BITS_KV8; one byte per element, kv_stream_stride and
+ * the layout still in elements): arguments, workspace, stride-0 chunk mode, split clamp and argument
+ * errors as above; every key and value is widened exactly to fp32 in registers (v_cvt_pk_f32_fp8), the
+ * softmax and the merges are the fp16 kernels' own code. */
+int ti_attn_decode_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache, int64_t kv_stream_stride,
+                      int max_seq, const int32_t* pos, int M, int heads, int kv_heads, int head_dim, int splits,
+                      float* workspace, uint16_t* out, ti_stream_t s);
+int ti_attn_decode_packed_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache,
+                             int64_t kv_stream_stride, int max_seq, const int32_t* pos, int M, int heads,
+                             int kv_heads, int head_dim, int splits, float* workspace, uint16_t* out,
+                             ti_stream_t s);
+int ti_attn_decode_partials_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache,
+                               int64_t kv_stream_stride, int max_seq, const int32_t* pos, int M, int heads,
+                               int kv_heads, int head_dim, int splits, uint16_t* part_o, float* part_ml,
+                               ti_stream_t s);
 /* One decode stream (bits 4 or 8; head_dim 64 GQA, or head_dim 128 with heads == kv_heads; 1024 <= K <=
  * 4096; ti_qkv_attn_supported): the QKV projection of the folded input (TI_X_F16_FOLDED: fx,
  * ss_in[0 .. n_ss)) with the TI_EPI_QKV_ROPE_KV epilogue's arithmetic -- the new K / V row into

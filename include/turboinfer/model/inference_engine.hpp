@@ -23,6 +23,8 @@
 // model's metadata or the environment (ModelMetadata::extra_params first, then the variable):
 //   * "turboinfer.weight_bits" / TI_WEIGHT_BITS: the weight format below (default 0 = auto);
 //   * "turboinfer.gpu_index" / TI_GPU_INDEX: the HIP device the engine binds (default 0).
+//   * "turboinfer.kv_bits" / TI_KV_BITS: 16 (fp16 KV cache, default) or 8 (e4m3 bytes, half the cache
+//     memory; outside the fp16 engine's logits contract); any other value throws.
 //   * "turboinfer.synthetic" / TI_SYNTHETIC: "1" lets a ModelData with metadata but no tensors (the
 //     reference's test programs) build the engine's seeded synthetic INT4 model of that shape
 //     (ti_engine_synth; the reference runs such a model on its placeholder fallbacks); without it

@@ -30,6 +30,7 @@ ARGMAX_SLOTS = 32
 GEMM_MAX_ROWS = 1024                # TI_GEMM_MAX_ROWS (include/ti_hip.h)
 BITS_G32 = 32                       # TI_BITS_G32 (include/ti_hip.h): group-32 weights (GGUF Q4_0 / Q8_0)
 BITS_AFF = 64                       # TI_BITS_AFF: affine group-32 int4 (GGUF Q4_1), with BITS_G32 | 4
+BITS_KV8 = 128                      # TI_BITS_KV8: e4m3 KV cache, OR-ed into an engine's bits (any weight format)
 SCALE_GROUP, SCALE_TENSOR, SCALE_UNIT = 0, 1, 2
 ROWS_CONCAT, ROWS_INTERLEAVE8 = 0, 1
 (W_Q, W_K, W_V, W_O, W_GATE, W_UP, W_DOWN, W_LM_HEAD, V_ATTN_NORM, V_FFN_NORM, V_OUT_NORM, E_EMBED) = range(12)
@@ -46,7 +47,8 @@ class Epilogue(C.Structure):
                 ("kv_stream_stride", C.c_int64), ("argmax", C.c_void_p), ("step_ctr", C.c_void_p),
                 ("advance", C.c_int32), ("n_ss", C.c_int32), ("ss_in", C.c_void_p),
                 ("fold_w", C.c_void_p), ("fold_x", C.c_void_p), ("fold_ss", C.c_void_p), ("out_packed", C.c_int32),
-                ("splitk_ws", C.c_void_p), ("splitk_bytes", C.c_int64), ("fold_packed", C.c_int32)]
+                ("splitk_ws", C.c_void_p), ("splitk_bytes", C.c_int64), ("fold_packed", C.c_int32),
+                ("kv_fp8", C.c_int32)]
 
 
 class StepArgs(C.Structure):
@@ -90,6 +92,8 @@ EXPORTED = [
     "ti_qkv_attn_partials", "ti_qkv_attn_part_o_elems", "ti_qkv_attn_part_ml_elems", "ti_engine_set_qkv_attn",
     "ti_qkv_attn_xchg_bytes", "ti_qkv_attn_supported", "ti_qkv_attn_error_offset",
     "ti_logprob_rows", "ti_engine_score",
+    "ti_attn_decode_f8", "ti_attn_decode_packed_f8", "ti_attn_decode_partials_f8", "ti_fill_kv_uniform_f8",
+    "ti_engine_read_kv",
 ]
 
 _lib = None
@@ -205,6 +209,11 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_engine_score"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_logprob_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
             L.ti_engine_score.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+        if hasattr(L, "ti_attn_decode_f8"):   # (older TI_LIB builds in A/B runs lack the e4m3 KV cache)
+            for n in ("ti_attn_decode_f8", "ti_attn_decode_packed_f8", "ti_attn_decode_partials_f8"):
+                getattr(L, n).argtypes = [vp, vp, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+            L.ti_fill_kv_uniform_f8.argtypes = [u64, C.c_uint32, i32, i32, i32, i32, vp, vp]
+            L.ti_engine_read_kv.argtypes = [vp, i32, i32, i32, i32, i32, vp]
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]
@@ -407,6 +416,14 @@ class Engine:
 
     def fill_kv(self, stream, n, seed):
         check(lib().ti_engine_fill_kv(self.h, stream, n, seed))
+
+    def read_kv(self, layer, stream, which, pos0, n) -> np.ndarray:
+        """Rows [pos0, pos0 + n) of a stream slot's K (which 0) or V (1) cache of `layer`, raw:
+        [kv_heads][n][head_dim] float16, or uint8 e4m3 bytes on a BITS_KV8 engine."""
+        kv8 = bool(self.cfg.bits & BITS_KV8)
+        out = np.empty((self.cfg.kv_heads, n, self.cfg.head_dim), np.uint8 if kv8 else np.float16)
+        check(lib().ti_engine_read_kv(self.h, layer, stream, which, pos0, n, _ptr(out)))
+        return out
 
     def generate(self, prompts, max_new, start_pos=None, want_logits=False):
         n = len(prompts)

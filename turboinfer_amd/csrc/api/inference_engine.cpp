@@ -44,6 +44,13 @@ int engine_option(const ModelMetadata& md, const char* key, const char* env, int
   return dflt;
 }
 
+// "turboinfer.kv_bits" / TI_KV_BITS: 16 (fp16 KV cache, the default) or 8 (e4m3, TI_BITS_KV8); any other value throws.
+int kv_bits_option(const ModelMetadata& md) {
+  const int b = engine_option(md, "turboinfer.kv_bits", "TI_KV_BITS", 16);
+  if (b != 8 && b != 16) throw std::runtime_error("InferenceEngine: kv_bits must be 8 (e4m3 KV cache) or 16 (fp16)");
+  return b;
+}
+
 [[noreturn]] void off_path(const std::string& what, const char* row) {
   throw std::runtime_error("InferenceEngine::" + what + ": not part of the MI355X decode hot path (SURVEY.md 8(f) " +
                            row + ")");
@@ -236,6 +243,7 @@ class InferenceEngineImpl {
   ti_engine* eng = nullptr;
   ti_engine_config cfg{};
   int capacity = 1;      // streams one device call holds
+  int kv_bits = 16;      // 8: e4m3 KV cache (TI_BITS_KV8 at ti_engine_create; cfg.bits stays the weight format)
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -327,13 +335,16 @@ class InferenceEngineImpl {
   // The device engine of cfg (filled in by the caller but for the stream capacity).
   void create(const InferenceConfig& c) {
     cfg.attn_splits = 0;
-    // streams held at once: the configured batch, bounded to 64 GiB of fp16 KV
-    const double kv_stream = 2.0 * cfg.layers * cfg.kv_heads * cfg.head_dim * 2.0 * cfg.max_seq;
+    if (compat) kv_bits = 16;   // the plumbing model has no KV cache
+    // streams held at once: the configured batch, bounded to 64 GiB of KV
+    const double kv_stream = 2.0 * cfg.layers * cfg.kv_heads * cfg.head_dim * (kv_bits / 8.0) * cfg.max_seq;
     capacity = (int)std::max<size_t>(1, std::min<size_t>(c.max_batch_size, (size_t)(64.0 * (1ull << 30) / kv_stream)));
     capacity = std::min(capacity, 64);
     cfg.max_batch = compat ? 1 : capacity;
     check(ti_init(cfg.device), "ti_init");
-    check(ti_engine_create(&cfg, &eng), "ti_engine_create");
+    ti_engine_config ec = cfg;
+    if (kv_bits == 8) ec.bits |= TI_BITS_KV8;
+    check(ti_engine_create(&ec, &eng), "ti_engine_create");
     // generate() ends its device loop at EOS (token id 2, inference_engine.cpp:759-764)
     if (!compat) check(ti_engine_set_stop(eng, kGenerateEos), "ti_engine_set_stop");
   }
@@ -355,6 +366,7 @@ class InferenceEngineImpl {
     cfg.eps = 1e-5f;
     const int bits = engine_option(md, "turboinfer.weight_bits", "TI_WEIGHT_BITS", 0);
     cfg.bits = bits == 8 || bits == 16 ? bits : 4;
+    kv_bits = kv_bits_option(md);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = 0;
     cfg.device = gpu;
@@ -427,6 +439,7 @@ class InferenceEngineImpl {
     cfg.rope_theta = md.rope_theta > 0.0f ? md.rope_theta : 10000.0f;
     cfg.eps = 1e-5f;
     cfg.bits = compat ? 16 : bits;
+    kv_bits = kv_bits_option(md);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = compat ? 1 : 0;
     cfg.device = gpu;
@@ -790,7 +803,7 @@ std::string InferenceEngine::performance_stats() const {
     os << "  Average Tokens/Second: " << (im.total_tokens / (im.total_time_ms / 1000.0f)) << "\n";
   os << "  Peak Tokens/Second: " << im.peak_tps << "\n";
   os << "  Device Memory: " << (memory_usage() / (1024.0 * 1024.0)) << " MB (weights " << (im.cfg.bits & ~(TI_BITS_G32 | TI_BITS_AFF))
-     << "-bit" << ((im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << ", fp16 KV, " << im.capacity
+     << "-bit" << ((im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << (im.kv_bits == 8 ? ", fp8 KV, " : ", fp16 KV, ") << im.capacity
      << " stream(s) x " << im.cfg.max_seq << " slots)\n";
   os << "  Mode: " << (im.compat ? "reference_compat (plumbing model)" : "llama decode") << "\n";
   return os.str();

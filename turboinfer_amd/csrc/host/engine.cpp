@@ -59,7 +59,7 @@ struct DevLayer {
   DevLinear qkv, o, gu, down;
   float* attn_norm = nullptr;
   float* ffn_norm = nullptr;
-  uint16_t* kc = nullptr;
+  uint16_t* kc = nullptr;   // fp16 elements; e4m3 bytes on a TI_BITS_KV8 engine (ti_engine::kv_at)
   uint16_t* vc = nullptr;
 };
 
@@ -146,7 +146,15 @@ struct ti_engine {
   uint64_t n_decode_steps = 0;   // step-graph replays (ti_engine_counters)
   uint64_t n_prefill_chunks = 0; // prompt chunks through enqueue_prefill
   int splits_max = 1;
-  int64_t kv_stride = 0;
+  int64_t kv_stride = 0;         // elements between the stream slots of a layer cache
+  // TI_BITS_KV8 (taken out of c.bits at creation, which then holds the weight format alone): the
+  // caches hold e4m3 bytes -- every QKV launch sets ti_epilogue.kv_fp8, the attention runs the _f8
+  // entry points (prompt chunks too, at stride 0), the fused QKV + attention launch is off
+  bool kv8 = false;
+  size_t kv_esz() const { return kv8 ? 1 : 2; }   // bytes per cache element
+  uint16_t* kv_at(uint16_t* base, size_t elems) const {
+    return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(base) + elems * kv_esz());
+  }
   uint16_t** kv_tab = nullptr;   // device [2 * layers]: every layer's K then V cache base (ti_kv_copy_slots)
   size_t weight_bytes = 0, kv_bytes = 0;
   std::map<std::pair<int, int>, hipGraphExec_t> graphs;  // (M, advance | sampled << 1)
@@ -252,16 +260,20 @@ inline void stamp_tag(int t) { g_stamp.tag = t; }
 int validate(const ti_engine_config& c) {
   if (c.vocab < 1 || c.hidden < 1 || c.layers < 0 || c.inter < 1 || c.max_seq < 1 || c.max_batch < 1)
     return ti_set_error(TI_ERR_ARG, "ti_engine_create: non-positive size in config");
-  if (c.compat) return TI_OK;
+  if (c.compat) {
+    if (c.bits & TI_BITS_KV8) return ti_set_error(TI_ERR_ARG, "ti_engine_create: TI_BITS_KV8 on a compat engine (no KV cache)");
+    return TI_OK;
+  }
   if (c.heads < 1 || c.kv_heads < 1 || c.heads % c.kv_heads)
     return ti_set_error(TI_ERR_ARG, "ti_engine_create: heads %d / kv_heads %d", c.heads, c.kv_heads);
   const int G = c.heads / c.kv_heads;
   if (G != 1 && G != 2 && G != 4 && G != 8) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: GQA group %d", G);
   if (c.head_dim != 64 && c.head_dim != 128) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: head_dim %d", c.head_dim);
-  if (c.bits != 4 && c.bits != 8 && c.bits != 16 && c.bits != (4 | TI_BITS_G32) && c.bits != (8 | TI_BITS_G32) &&
-      c.bits != (4 | TI_BITS_G32 | TI_BITS_AFF))
+  const int wbits = c.bits & ~TI_BITS_KV8;   // the weight format; TI_BITS_KV8 goes with every one
+  if (wbits != 4 && wbits != 8 && wbits != 16 && wbits != (4 | TI_BITS_G32) && wbits != (8 | TI_BITS_G32) &&
+      wbits != (4 | TI_BITS_G32 | TI_BITS_AFF))
     return ti_set_error(TI_ERR_ARG, "ti_engine_create: bits %d (4, 8, 16; 4 or 8 | TI_BITS_G32; 4 | TI_BITS_G32 | "
-                        "TI_BITS_AFF)", c.bits);
+                        "TI_BITS_AFF; each | TI_BITS_KV8)", c.bits);
   const int qd = c.heads * c.head_dim, kvd = c.kv_heads * c.head_dim;
   if (c.hidden % 128 || qd % 128 || c.inter % 128)
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: hidden, heads*head_dim and inter must be multiples of 128");
@@ -302,8 +314,9 @@ int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind
     ti_epilogue ep = epi;
     ep.out = static_cast<char*>(epi.out) + (size_t)m0 * epi.ldo * out_elem;
     if (ep.pos) ep.pos += m0;
-    if (ep.k_cache) ep.k_cache += (size_t)m0 * ep.kv_stream_stride;
-    if (ep.v_cache) ep.v_cache += (size_t)m0 * ep.kv_stream_stride;
+    if (ep.k_cache) ep.k_cache = e->kv_at(ep.k_cache, (size_t)m0 * ep.kv_stream_stride);
+    if (ep.v_cache) ep.v_cache = e->kv_at(ep.v_cache, (size_t)m0 * ep.kv_stream_stride);
+    if (ep.k_cache) ep.kv_fp8 = e->kv8 ? 1 : 0;   // every QKV launch of a TI_BITS_KV8 engine
     if (ep.argmax) ep.argmax += (size_t)m0 * TI_ARGMAX_SLOTS;
     if (!(last_gets_ctr && m0 + mm >= M)) ep.step_ctr = nullptr;
     ep.splitk_ws = e->splitk_ws;
@@ -314,6 +327,26 @@ int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind
   return TI_OK;
 }
 
+
+// The decode attention over the engine's caches, in their element type.
+int attn_merged(ti_engine* e, bool packed, const uint16_t* kc, const uint16_t* vc, int64_t stride, int M, int splits) {
+  const ti_engine_config& c = e->c;
+  if (e->kv8)
+    return (packed ? ti_attn_decode_packed_f8 : ti_attn_decode_f8)(
+        e->q, reinterpret_cast<const uint8_t*>(kc), reinterpret_cast<const uint8_t*>(vc), stride, c.max_seq, e->pos, M,
+        c.heads, c.kv_heads, c.head_dim, splits, e->ws, e->attn, e->s);
+  return (packed ? ti_attn_decode_packed : ti_attn_decode)(e->q, kc, vc, stride, c.max_seq, e->pos, M, c.heads,
+                                                            c.kv_heads, c.head_dim, splits, e->ws, e->attn, e->s);
+}
+int attn_partials(ti_engine* e, const uint16_t* kc, const uint16_t* vc, int M, int splits) {
+  const ti_engine_config& c = e->c;
+  if (e->kv8)
+    return ti_attn_decode_partials_f8(e->q, reinterpret_cast<const uint8_t*>(kc), reinterpret_cast<const uint8_t*>(vc),
+                                      e->kv_stride, c.max_seq, e->pos, M, c.heads, c.kv_heads, c.head_dim, splits,
+                                      e->part_o, e->part_ml, e->s);
+  return ti_attn_decode_partials(e->q, kc, vc, e->kv_stride, c.max_seq, e->pos, M, c.heads, c.kv_heads, c.head_dim,
+                                 splits, e->part_o, e->part_ml, e->s);
+}
 
 int get_graph(ti_engine* e, int M, int advance, hipGraphExec_t* out);
 
@@ -380,7 +413,8 @@ int qa_fault_check(ti_engine* e) {
 // int8 / int4 group-128 weights, head_dim 64 GQA (TinyLlama-1.1B) or head_dim 128 MHA (Llama-2-7B).
 bool qa_usable(ti_engine* e, int M) {
   const ti_engine_config& c = e->c;
-  if (!e->qa_on || M != 1 || !fold_usable(e, M) || !part_usable(e, M)) return false;
+  // (a TI_BITS_KV8 engine: off -- the launch attends the step's own key unquantised, a different function)
+  if (!e->qa_on || e->kv8 || M != 1 || !fold_usable(e, M) || !part_usable(e, M)) return false;
   // all heads x splits workgroups resident at once for the in-launch q exchange
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -501,8 +535,7 @@ int enqueue_step(ti_engine* e, int M, int advance) {
       stamp_tag(TI_STAMP_TAG_QKV);
       TI_TRY(gemm(L.qkv, e->h, TI_X_F32_RMSNORM, H, 4, L.attn_norm, ep, 4, false));
       stamp_tag(TI_STAMP_TAG_ATTN);
-      TI_TRY(ti_attn_decode_partials(e->q, L.kc, L.vc, e->kv_stride, c.max_seq, e->pos, M, c.heads, c.kv_heads,
-                                     c.head_dim, e->splits_for(M), e->part_o, e->part_ml, e->s));
+      TI_TRY(attn_partials(e, L.kc, L.vc, M, e->splits_for(M)));
       eo.ss_in = e->part_ml;
       eo.n_ss = e->splits_for(M);
       eo.head_dim = c.head_dim;
@@ -512,9 +545,7 @@ int enqueue_step(ti_engine* e, int M, int advance) {
       stamp_tag(TI_STAMP_TAG_QKV);
       TI_TRY(gemm(L.qkv, e->h, TI_X_F32_RMSNORM, H, 4, L.attn_norm, ep, 4, false));
       stamp_tag(TI_STAMP_TAG_ATTN);
-      TI_TRY((pk ? ti_attn_decode_packed : ti_attn_decode)(e->q, L.kc, L.vc, e->kv_stride, c.max_seq, e->pos, M,
-                                                           c.heads, c.kv_heads, c.head_dim, e->splits_for(M), e->ws,
-                                                           e->attn, e->s));
+      TI_TRY(attn_merged(e, pk, L.kc, L.vc, e->kv_stride, M, e->splits_for(M)));
       stamp_tag(TI_STAMP_TAG_O);
       TI_TRY(gemm(L.o, e->attn, pk ? TI_X_F16_PACKED : TI_X_F16, qd, 2, nullptr, eo, 4, false));
     }
@@ -565,7 +596,8 @@ static bool prefill_attn_on();
 // chunks run ti_attn_prefill, no workspace), all chunk sizes when TI_ATTN_PREFILL=0.
 size_t ws_bytes(const ti_engine* e) {
   const ti_engine_config& c = e->c;
-  const int R = prefill_attn_on() ? std::min(e->rows_cap, std::max(c.max_batch, 64)) : e->rows_cap;
+  // (TI_BITS_KV8: every prompt chunk runs the split kernel)
+  const int R = prefill_attn_on() && !e->kv8 ? std::min(e->rows_cap, std::max(c.max_batch, 64)) : e->rows_cap;
   size_t b = 0;
   for (int M = 1; M <= R; ++M) b = std::max(b, ti_attn_workspace_bytes(M, c.heads, c.head_dim, e->splits_for(M)));
   return b;
@@ -614,8 +646,8 @@ int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
   const int H = c.hidden, qd = e->qd(), kvd = e->kvd(), I = c.inter;
   for (int l = 0; l < c.layers; ++l) {
     DevLayer& L = e->layer[l];
-    uint16_t* kc = L.kc + (size_t)m * e->kv_stride;
-    uint16_t* vc = L.vc + (size_t)m * e->kv_stride;
+    uint16_t* kc = e->kv_at(L.kc, (size_t)m * e->kv_stride);
+    uint16_t* vc = e->kv_at(L.vc, (size_t)m * e->kv_stride);
     ti_epilogue ep{};
     ep.kind = TI_EPI_QKV_ROPE_KV;
     ep.ldo = qd;
@@ -631,12 +663,12 @@ int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
     ep.kv_stream_stride = 0;
     TI_TRY(gemm_rows(e, L.qkv, rows, e->h, TI_X_F32_RMSNORM, H, L.attn_norm, ep, 4, false));
     const bool pk = packed_rows(e, rows);
-    if (!pk && prefill_attn_on())   // row-major chunk: one pass over the prefix per 16 rows (MFMA)
+    // (an e4m3 cache: the decode kernel at stride 0 -- every row reads its keys, its own included, from
+    // the quantised cache, as a decode step would; ti_attn_prefill reads fp16 only)
+    if (!pk && prefill_attn_on() && !e->kv8)   // row-major chunk: one pass over the prefix per 16 rows (MFMA)
       TI_TRY(ti_attn_prefill(e->q, kc, vc, c.max_seq, e->pos, rows, c.heads, c.kv_heads, c.head_dim, e->attn, e->s));
     else
-      TI_TRY((pk ? ti_attn_decode_packed : ti_attn_decode)(e->q, kc, vc, 0, c.max_seq, e->pos, rows, c.heads,
-                                                           c.kv_heads, c.head_dim, e->splits_for(rows), e->ws,
-                                                           e->attn, e->s));
+      TI_TRY(attn_merged(e, pk, kc, vc, 0, rows, e->splits_for(rows)));
     ti_epilogue eo{};
     eo.kind = TI_EPI_RESID_F32;
     eo.ldo = H;
@@ -727,6 +759,8 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
   TI_TRY(ti_init(cfg->device));
   ti_engine* e = new ti_engine();
   e->c = *cfg;
+  e->kv8 = !cfg->compat && (cfg->bits & TI_BITS_KV8) != 0;
+  e->c.bits &= ~TI_BITS_KV8;   // from here on: the weight format
   const ti_engine_config& c = e->c;
   auto fail = [&](int rc) { delete e; return rc; };
   if (hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking) != hipSuccess)
@@ -747,9 +781,10 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
       if ((rc = e->alloc_linear(L.qkv, H, qd + 2 * kvd)) || (rc = e->alloc_linear(L.o, qd, H)) ||
           (rc = e->alloc_linear(L.gu, H, 2 * I)) || (rc = e->alloc_linear(L.down, I, H)) ||
           (rc = e->alloc_t(&L.attn_norm, (size_t)H)) || (rc = e->alloc_t(&L.ffn_norm, (size_t)H)) ||
-          (rc = e->alloc_t(&L.kc, (size_t)B * e->kv_stride)) || (rc = e->alloc_t(&L.vc, (size_t)B * e->kv_stride)))
+          (rc = e->alloc(reinterpret_cast<void**>(&L.kc), (size_t)B * e->kv_stride * e->kv_esz())) ||
+          (rc = e->alloc(reinterpret_cast<void**>(&L.vc), (size_t)B * e->kv_stride * e->kv_esz())))
         return fail(rc);
-      e->kv_bytes += (size_t)2 * B * e->kv_stride * 2;
+      e->kv_bytes += (size_t)2 * B * e->kv_stride * e->kv_esz();
     }
     if ((rc = e->alloc_linear(e->lm, H, V)) || (rc = e->alloc_t(&e->emb, (size_t)V * H)) ||
         (rc = e->alloc_t(&e->out_norm, (size_t)H)) || (rc = e->alloc_t(&e->rope_cs, (size_t)c.max_seq * hd)))
@@ -971,11 +1006,32 @@ int ti_engine_fill_kv(ti_engine* e, int stream, int n, uint64_t seed) {
     return ti_set_error(TI_ERR_ARG, "ti_engine_fill_kv: stream %d n %d", stream, n);
   for (int l = 0; l < e->c.layers; ++l) {
     DevLayer& L = e->layer[l];
-    TI_TRY(ti_fill_kv_uniform(seed, tid_kv(l, 0), n, e->c.kv_heads, e->c.head_dim, e->c.max_seq,
-                              L.kc + (size_t)stream * e->kv_stride, e->s));
-    TI_TRY(ti_fill_kv_uniform(seed, tid_kv(l, 1), n, e->c.kv_heads, e->c.head_dim, e->c.max_seq,
-                              L.vc + (size_t)stream * e->kv_stride, e->s));
+    uint16_t* caches[2] = {e->kv_at(L.kc, (size_t)stream * e->kv_stride), e->kv_at(L.vc, (size_t)stream * e->kv_stride)};
+    for (int v = 0; v < 2; ++v) {
+      if (e->kv8)
+        TI_TRY(ti_fill_kv_uniform_f8(seed, tid_kv(l, v), n, e->c.kv_heads, e->c.head_dim, e->c.max_seq,
+                                     reinterpret_cast<uint8_t*>(caches[v]), e->s));
+      else
+        TI_TRY(ti_fill_kv_uniform(seed, tid_kv(l, v), n, e->c.kv_heads, e->c.head_dim, e->c.max_seq, caches[v], e->s));
+    }
   }
+  return ti_stream_sync(e->s);
+}
+
+int ti_engine_read_kv(ti_engine* e, int layer, int stream, int which, int pos0, int n, void* out) {
+  if (!e || e->c.compat) return ti_set_error(TI_ERR_ARG, "ti_engine_read_kv: no KV cache");
+  const ti_engine_config& c = e->c;
+  if (!out || layer < 0 || layer >= c.layers || stream < 0 || stream >= c.max_batch || (which != 0 && which != 1) ||
+      pos0 < 0 || n < 1 || pos0 > c.max_seq - n)
+    return ti_set_error(TI_ERR_ARG, "ti_engine_read_kv: layer %d stream %d which %d pos0 %d n %d", layer, stream, which,
+                        pos0, n);
+  DeviceScope bind_(e);
+  const DevLayer& L = e->layer[(size_t)layer];
+  const size_t esz = e->kv_esz(), row = (size_t)n * c.head_dim * esz;
+  const char* base = reinterpret_cast<const char*>(which ? L.vc : L.kc) + (size_t)stream * e->kv_stride * esz;
+  E_CHECK(hipMemcpy2DAsync(out, row, base + (size_t)pos0 * c.head_dim * esz, (size_t)c.max_seq * c.head_dim * esz, row,
+                           (size_t)c.kv_heads, hipMemcpyDeviceToHost, e->s),
+          "hipMemcpy2DAsync(read_kv)");
   return ti_stream_sync(e->s);
 }
 
@@ -1226,8 +1282,11 @@ std::vector<float> beam_top_p(const std::vector<float>& probs, float p) {
 // Copy slot `src`'s cache positions [0, n) into slot `dst`, every layer, K and V.
 int fork_slot(ti_engine* e, int src, int dst, int n) {
   const ti_engine_config& c = e->c;
-  return ti_kv_copy_slots(e->kv_tab, 2 * c.layers, (int64_t)src * e->kv_stride, (int64_t)dst * e->kv_stride,
-                          c.kv_heads, (int64_t)c.max_seq * c.head_dim, (int64_t)n * c.head_dim, e->s);
+  // an e4m3 cache goes as 2-byte units: half the element counts (ti_hip.h; head_dim >= 64 keeps every
+  // count a multiple of 8 units)
+  const int64_t d = e->kv8 ? 2 : 1;
+  return ti_kv_copy_slots(e->kv_tab, 2 * c.layers, (int64_t)src * e->kv_stride / d, (int64_t)dst * e->kv_stride / d,
+                          c.kv_heads, (int64_t)c.max_seq * c.head_dim / d, (int64_t)n * c.head_dim / d, e->s);
 }
 }  // namespace
 
@@ -1740,12 +1799,8 @@ int ti_engine_time_kernel(ti_engine* e, int which, int n, int kv_len, int reps, 
     TI_TRY(setup(L, W, x, xk, ldx, nw, ep));
     // (the one lm_head, 68 MB at 7B, fits the Infinity Cache: back-to-back it runs warm)
     if (which == 5 && part)
-      return ti_attn_decode_partials(e->q, L.kc, L.vc, e->kv_stride, c.max_seq, e->pos, n, c.heads, c.kv_heads,
-                                     c.head_dim, e->splits_for(n), e->part_o, e->part_ml, e->s);
-    if (which == 5)
-      return (packed_rows(e, n) ? ti_attn_decode_packed : ti_attn_decode)(e->q, L.kc, L.vc, e->kv_stride, c.max_seq,
-                                                                           e->pos, n, c.heads, c.kv_heads, c.head_dim,
-                                                                           e->splits_for(n), e->ws, e->attn, e->s);
+      return attn_partials(e, L.kc, L.vc, n, e->splits_for(n));
+    if (which == 5) return attn_merged(e, packed_rows(e, n), L.kc, L.vc, e->kv_stride, n, e->splits_for(n));
     return gemm_rows(e, *W, n, x, xk, ldx, nw, ep, which == 2 ? 2 : 4, false);
   };
   // The `reps` launches are captured once into a graph and the graph is replayed `rounds`
@@ -1786,12 +1841,12 @@ int ti_engine_time_kernel(ti_engine* e, int which, int n, int kv_len, int reps, 
   // per projection (all row chunks of it, and the rms_norm prep of the batched path)
   *avg_us = (double)ms * 1000.0 / ((double)reps * rounds);
   if (which == 5) {
-    *bytes = 2.0 * n * (double)kvd * kv_len * 2.0 + (double)n * qd * (4 + 2);
+    *bytes = 2.0 * n * (double)kvd * kv_len * (double)e->kv_esz() + (double)n * qd * (4 + 2);
   } else if (which == 6) {   // every layer's weights + scales, K/V read at kv_len, K/V row written
     double wl = 0.0;
     for (const DevLinear* L : {&e->layer[0].qkv, &e->layer[0].o, &e->layer[0].gu, &e->layer[0].down})
       wl += (double)ti_wpack_tile_bytes(c.bits, L->K, L->N) + (double)ti_wpack_scale_bytes(c.bits, L->K, L->N);
-    *bytes = c.layers * (wl + 2.0 * (double)kvd * kv_len * 2.0 + 2.0 * kvd * 2.0);
+    *bytes = c.layers * (wl + 2.0 * (double)kvd * kv_len * (double)e->kv_esz() + 2.0 * kvd * (double)e->kv_esz());
   } else {
     const double wbytes = (double)ti_wpack_tile_bytes(c.bits, W->K, W->N) + (double)ti_wpack_scale_bytes(c.bits, W->K, W->N);
     *bytes = wbytes + (double)n * W->K * (xk == TI_X_F16 || xk == TI_X_F16_FOLDED ? 2 : 4);

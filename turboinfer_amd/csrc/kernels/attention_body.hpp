@@ -8,10 +8,17 @@
 namespace ti {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// The DPL cache elements a lane holds per key row: 8 fp16 in 16 bytes; of an e4m3 cache (KV8, TI_BITS_KV8)
+// 8 in 8 bytes -- the fp16 lane layout and index arithmetic, half the bytes per load -- or 16 in 16 bytes
+// (DPL 16: half the lanes per key row, twice the keys per wave-load; used where it measured faster).
+template <bool KV8, int DPL> struct KvRow { typedef u32x4 reg; static constexpr int kElemBytes = KV8 ? 1 : 2; };
+template <> struct KvRow<true, 8> { typedef u32x2 reg; static constexpr int kElemBytes = 1; };
 
 struct AttnArgs {
   const float* q;
-  const uint16_t* kc;
+  const uint16_t* kc;   // fp16 elements; e4m3 bytes in the KV8 instances (offsets counted in elements)
   const uint16_t* vc;
   const int32_t* pos;
   float* ws;
@@ -78,6 +85,27 @@ __device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
   }
 }
 
+// 8 e4m3 bytes -> 8 floats, exactly: four v_cvt_pk_f32_fp8
+__device__ __forceinline__ void unpack8(const u32x2 v, float (&f)[8]) {
+  const uint32_t w0 = v[0], w1 = v[1];   // (elements copied out first, as above)
+  e4m3x4_to_f32(w0, f[0], f[1], f[2], f[3]);
+  e4m3x4_to_f32(w1, f[4], f[5], f[6], f[7]);
+}
+
+// 16 e4m3 bytes -> 16 floats
+__device__ __forceinline__ void unpack16(const u32x4 v, float (&f)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t w = v[i];
+    e4m3x4_to_f32(w, f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]);
+  }
+}
+template <int DPL, class T>
+__device__ __forceinline__ void unpack_row(const T v, float (&f)[DPL]) {
+  if constexpr (DPL == 16) unpack16(v, f);
+  else unpack8(v, f);
+}
+
 // Write-through (sc1) 16-byte buffer store / load for the split hand-off (aux bit 4 = sc1
 // on gfx950); builtins, so the compiler counts them for its waitcnts.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rsrc(const float* base) {
@@ -93,7 +121,8 @@ __host__ __device__ constexpr int attn_max_splits(int G, int HD) { return (48 * 
 #ifndef TI_ATTN_NT
 #define TI_ATTN_NT 1
 #endif
-__device__ __forceinline__ u32x4 ld_kv(const u32x4* p) {
+template <class T>
+__device__ __forceinline__ T ld_kv(const T* p) {
 #if TI_ATTN_NT
   return __builtin_nontemporal_load(p);
 #else
@@ -118,14 +147,18 @@ __device__ __forceinline__ float groups_sum(float v) {
 // previous slot's softmax (tied to its running sum), so the scores of later slots cannot be
 // hoisted to the top of the pass -- where they would wait for the loads issued last and drain the
 // ring once per pass -- and each slot waits only for its own loads.
-__device__ __forceinline__ void ring_pin(u32x4& k, u32x4& v, float& prev) {
+template <class T>
+__device__ __forceinline__ void ring_pin(T& k, T& v, float& prev) {
   asm volatile("" : "+v"(k), "+v"(v), "+v"(prev));
 }
 
-template <int HD, int G, int R, bool HP, int NW = kAttnWaves, bool ROT = false>   // HP: head-parallel lanes (G >= 4, HD / (64 / G) == 8; see below)
+template <int HD, int G, int R, bool HP, int NW = kAttnWaves, bool ROT = false, bool KV8 = false, int DPL = 8>   // HP: head-parallel lanes (G >= 4, HD / (64 / G) == 8; see below)
 __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, int kvh, int m) {
-  static_assert(!HP || (G >= 4 && HD / (64 / G) == 8), "head-parallel layout: 8 dims per lane");
-  constexpr int LPK = HD / 8;       // lanes per key row
+  typedef typename KvRow<KV8, DPL>::reg kv_reg;
+  constexpr int EB = KvRow<KV8, DPL>::kElemBytes;
+  static_assert(!HP || (G >= 4 && HD / (64 / G) == 8 && DPL == 8), "head-parallel layout: 8 dims per lane");
+  static_assert(DPL == 8 || (DPL == 16 && KV8 && HD / DPL >= 8), "16 dims per lane: e4m3 rows of at least 8 lanes");
+  constexpr int LPK = HD / DPL;     // lanes per key row
   constexpr int KPW = 64 / LPK;     // keys per slot (wave-load)
   __shared__ float s_m[NW][G], s_l[NW][G];
   __shared__ __attribute__((aligned(16))) float s_acc[NW][G][HD];
@@ -137,10 +170,10 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int dl = lane % LPK, kg = lane / LPK;
   const int L = a.pos[m] + 1;
-  // K/V of this workgroup's (stream, kv-head): [max_seq][HD] fp16 from wg_off
+  // K/V of this workgroup's (stream, kv-head): [max_seq][HD] elements (fp16, or e4m3 bytes) from wg_off
   const int64_t wg_off = (int64_t)m * a.stride + (int64_t)(kvh >> a.kv_shift) * a.max_seq * HD;
-  auto ld_k = [&](int64_t elem) -> u32x4 { return ld_kv((const u32x4*)(a.kc + wg_off + elem)); };
-  auto ld_v = [&](int64_t elem) -> u32x4 { return ld_kv((const u32x4*)(a.vc + wg_off + elem)); };
+  auto ld_k = [&](int64_t elem) -> kv_reg { return ld_kv((const kv_reg*)((const char*)a.kc + (wg_off + elem) * EB)); };
+  auto ld_v = [&](int64_t elem) -> kv_reg { return ld_kv((const kv_reg*)((const char*)a.vc + (wg_off + elem) * EB)); };
   auto ld_q4 = [&](size_t elem) -> float4 { return *(const float4*)(a.q + elem); };
   // fp16 output element idx
   auto store_out = [&](size_t idx, float val) {
@@ -164,7 +197,7 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
     const int nkey = s1 > s0 ? s1 - s0 : 0;
     const int total = wave < nkey ? (nkey - wave + NW - 1) / NW : 0;   // this wave's keys
     int rj = 0;
-    u32x4 kr[R], vr[R];
+    kv_reg kr[R], vr[R];
     auto refill = [&](int s) {
       const int key = min(s0 + wave + NW * (rj < total ? rj : max(total - 1, 0)), max(s1 - 1, 0));
       ++rj;
@@ -184,7 +217,7 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc1[e] = 0.0f;
     int ci = 0;
-    auto consume = [&](const u32x4& kv, const u32x4& vv) {
+    auto consume = [&](const kv_reg& kv, const kv_reg& vv) {
       const bool valid = ci < total;
       ++ci;
       float kf[8], vf[8];
@@ -235,51 +268,55 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
       if constexpr (ROT) j = j + rot >= nslot ? j + rot - nslot : j + rot;
       return s0 + j * KPW + kg;
     };
-    u32x4 kr[R], vr[R];
+    kv_reg kr[R], vr[R];
     auto refill = [&](int s) {
       const int key = min(slot_key(rj < total ? rj : max(total - 1, 0)), max(s1 - 1, 0));
       ++rj;
-      kr[s] = ld_k((int64_t)key * HD + dl * 8);
-      vr[s] = ld_v((int64_t)key * HD + dl * 8);
+      kr[s] = ld_k((int64_t)key * HD + dl * DPL);
+      vr[s] = ld_v((int64_t)key * HD + dl * DPL);
     };
-    float4 qr[G][2];
+    constexpr int QV = DPL / 4;
+    float4 qr[G][QV];
   #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const size_t qe = (size_t)m * a.heads * HD + (size_t)(kvh * G + g) * HD + dl * 8;
-      qr[g][0] = ld_q4(qe);
-      qr[g][1] = ld_q4(qe + 4);
+      const size_t qe = (size_t)m * a.heads * HD + (size_t)(kvh * G + g) * HD + dl * DPL;
+  #pragma unroll
+      for (int i = 0; i < QV; ++i) qr[g][i] = ld_q4(qe + 4 * i);
     }
   #pragma unroll
     for (int s = 0; s < R; ++s) refill(s);
 
-    float q[G][8];
+    float q[G][DPL];
   #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const float4 q0 = qr[g][0], q1 = qr[g][1];
-      q[g][0] = q0.x * a.scale; q[g][1] = q0.y * a.scale; q[g][2] = q0.z * a.scale; q[g][3] = q0.w * a.scale;
-      q[g][4] = q1.x * a.scale; q[g][5] = q1.y * a.scale; q[g][6] = q1.z * a.scale; q[g][7] = q1.w * a.scale;
+  #pragma unroll
+      for (int i = 0; i < QV; ++i) {
+        const float4 qi = qr[g][i];
+        q[g][4 * i] = qi.x * a.scale; q[g][4 * i + 1] = qi.y * a.scale;
+        q[g][4 * i + 2] = qi.z * a.scale; q[g][4 * i + 3] = qi.w * a.scale;
+      }
     }
-    float mrun[G], lrun[G], acc[G][8];
+    float mrun[G], lrun[G], acc[G][DPL];
   #pragma unroll
     for (int g = 0; g < G; ++g) {
       mrun[g] = -INFINITY;
       lrun[g] = 0.0f;
   #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[g][e] = 0.0f;
+      for (int e = 0; e < DPL; ++e) acc[g][e] = 0.0f;
     }
 
     int ci = 0;   // compute cursor (slot index of this wave)
-    auto consume = [&](const u32x4& kv, const u32x4& vv) {
+    auto consume = [&](const kv_reg& kv, const kv_reg& vv) {
       const bool valid = slot_key(ci) < s1;
       ++ci;
-      float kf[8], vf[8];
-      unpack8(kv, kf);
-      unpack8(vv, vf);
+      float kf[DPL], vf[DPL];
+      unpack_row<DPL>(kv, kf);
+      unpack_row<DPL>(vv, vf);
   #pragma unroll
       for (int g = 0; g < G; ++g) {
         float d = 0.0f;
   #pragma unroll
-        for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], kf[e], d);
+        for (int e = 0; e < DPL; ++e) d = fmaf(q[g][e], kf[e], d);
         d = group_sum<LPK>(d);
         const float sc = valid ? d : -INFINITY;
         const float mn = fmaxf(mrun[g], sc);
@@ -288,7 +325,7 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
         lrun[g] = fmaf(lrun[g], alpha, p);
         mrun[g] = mn;
   #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] = fmaf(p, vf[e], acc[g][e] * alpha);
+        for (int e = 0; e < DPL; ++e) acc[g][e] = fmaf(p, vf[e], acc[g][e] * alpha);
       }
     };
     int j0 = 0;
@@ -312,7 +349,7 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
       const float f = mrun[g] == -INFINITY ? 0.0f : __expf(mrun[g] - mx);
       const float l = groups_sum<LPK>(lrun[g] * f);
   #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[g][e] = groups_sum<LPK>(acc[g][e] * f);
+      for (int e = 0; e < DPL; ++e) acc[g][e] = groups_sum<LPK>(acc[g][e] * f);
       mrun[g] = mx;
       lrun[g] = l;
     }
@@ -320,7 +357,7 @@ __device__ __forceinline__ void attn_split_body(const AttnArgs& a, int split, in
   #pragma unroll
       for (int g = 0; g < G; ++g)
   #pragma unroll
-        for (int e = 0; e < 8; ++e) s_acc[wave][g][dl * 8 + e] = acc[g][e];
+        for (int e = 0; e < DPL; ++e) s_acc[wave][g][dl * DPL + e] = acc[g][e];
     }
     if (lane == 0) {
   #pragma unroll

@@ -49,6 +49,25 @@ __device__ inline uint16_t f2h_soft(float f) {
   return s | (uint16_t)hb;
 }
 
+// ---------------------------------------------------------------- e4m3 helpers (8-bit KV cache)
+// OCP e4m3fn, no scale: byte = round-to-nearest-even e4m3 of min(max(x, -448), 448),
+// two elements per v_cvt_pk_fp8_f32 (gfx950 converts the OCP format).  The clamp is explicit: the
+// instruction's own overflow result depends on the mode register.  a -> bits 0-7, b -> bits 8-15.
+__device__ __forceinline__ uint32_t f2e4m3x2(float a, float b) {
+  a = __builtin_fminf(__builtin_fmaxf(a, -448.0f), 448.0f);
+  b = __builtin_fminf(__builtin_fmaxf(b, -448.0f), 448.0f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
+}
+__device__ __forceinline__ uint8_t f2e4m3(float a) { return (uint8_t)(f2e4m3x2(a, 0.0f) & 0xffu); }
+__device__ __forceinline__ uint32_t f2e4m3x4(float a, float b, float c, float d) {
+  return f2e4m3x2(a, b) | (f2e4m3x2(c, d) << 16);
+}
+// the 4 e4m3 bytes of w -> fp32, exactly (v_cvt_pk_f32_fp8 on the low / high half)
+__device__ __forceinline__ void e4m3x4_to_f32(uint32_t w, float& f0, float& f1, float& f2, float& f3) {
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  f0 = lo[0]; f1 = lo[1]; f2 = hi[0]; f3 = hi[1];
+}
+
 // ------------------------------------------------------------ wave reductions
 template <int WIDTH>
 __device__ __forceinline__ float wave_sum_xor(float v) {

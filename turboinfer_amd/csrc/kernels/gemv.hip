@@ -275,7 +275,9 @@ __device__ __forceinline__ void epilogue(const GemvArgs& a, int nt, int tl, int 
         const int c = ng - e.q_dim - (is_k ? 0 : e.kv_dim);
         const int kvh = c / hd, d = c - kvh * hd;
         uint16_t* cache = is_k ? e.k_cache : e.v_cache;
-        cache[(size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d] = f2h(r);
+        const size_t ci = (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d;
+        if (e.kv_fp8) ((uint8_t*)cache)[ci] = f2e4m3(r);
+        else cache[ci] = f2h(r);
       }
       break;
     }
@@ -937,12 +939,16 @@ __device__ __forceinline__ void epilogue_mb(const GemvArgs& a, int nt, int m, in
           ((float*)e.out)[(size_t)m * e.ldo + ng] = r;
         } else {
           const int kvh = (ng - e.q_dim) / hd;
-          e.k_cache[(size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d] = f2h(r);
+          const size_t ci = (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d;
+          if (e.kv_fp8) ((uint8_t*)e.k_cache)[ci] = f2e4m3(r);
+          else e.k_cache[ci] = f2h(r);
         }
       } else {
         const int c = ng - e.q_dim - e.kv_dim;
         const int kvh = c / hd, d = c - kvh * hd;
-        e.v_cache[(size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d] = f2h(v);
+        const size_t ci = (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d;
+        if (e.kv_fp8) ((uint8_t*)e.v_cache)[ci] = f2e4m3(v);
+        else e.v_cache[ci] = f2h(v);
       }
       break;
     }
@@ -1713,12 +1719,20 @@ __device__ __forceinline__ void tile_epilogue_lds(const GemvArgs& a, int tn, int
         if (in_q) {
           *(float4*)((float*)e.out + (size_t)m * e.ldo + ng) = make_float4(r0, r1, r2, r3);
         } else {
-          *(uint2*)(e.k_cache + (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d) =
-              make_uint2(f2h(r0) | ((uint32_t)f2h(r1) << 16), f2h(r2) | ((uint32_t)f2h(r3) << 16));
+          const size_t ci = (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d;
+          if (e.kv_fp8)   // 4 elements -> one 32-bit store
+            *(uint32_t*)((uint8_t*)e.k_cache + ci) = f2e4m3x4(r0, r1, r2, r3);
+          else
+            *(uint2*)(e.k_cache + ci) =
+                make_uint2(f2h(r0) | ((uint32_t)f2h(r1) << 16), f2h(r2) | ((uint32_t)f2h(r3) << 16));
         }
       } else {
-        *(uint2*)(e.v_cache + (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d) =
-            make_uint2(f2h(v.x) | ((uint32_t)f2h(v.y) << 16), f2h(v.z) | ((uint32_t)f2h(v.w) << 16));
+        const size_t ci = (size_t)m * e.kv_stream_stride + ((size_t)kvh * e.max_seq + p) * hd + d;
+        if (e.kv_fp8)
+          *(uint32_t*)((uint8_t*)e.v_cache + ci) = f2e4m3x4(v.x, v.y, v.z, v.w);
+        else
+          *(uint2*)(e.v_cache + ci) =
+              make_uint2(f2h(v.x) | ((uint32_t)f2h(v.y) << 16), f2h(v.z) | ((uint32_t)f2h(v.w) << 16));
       }
     }
   }
@@ -2641,6 +2655,7 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
           (epi->head_dim & 1) || epi->q_dim + 2 * epi->kv_dim != N || epi->q_dim % epi->head_dim ||
           epi->kv_dim % epi->head_dim || epi->ldo < epi->q_dim)
         return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: inconsistent QKV epilogue");
+      if (epi->kv_fp8 != 0 && epi->kv_fp8 != 1) return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: kv_fp8 %d", epi->kv_fp8);
       break;
     case TI_EPI_LOGITS_ARGMAX:
       if (!epi->argmax || epi->ldo < N) return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: argmax/ldo");
@@ -2658,8 +2673,9 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
       ti_epilogue ep = *epi;
       ep.out = static_cast<char*>(epi->out) + (size_t)m0 * epi->ldo * out_elem;
       if (ep.pos) ep.pos += m0;
-      if (ep.k_cache) ep.k_cache += (size_t)m0 * ep.kv_stream_stride;
-      if (ep.v_cache) ep.v_cache += (size_t)m0 * ep.kv_stream_stride;
+      const size_t kv_esz = ep.kv_fp8 ? 1 : 2;   // bytes per cache element
+      if (ep.k_cache) ep.k_cache = (uint16_t*)((char*)ep.k_cache + (size_t)m0 * ep.kv_stream_stride * kv_esz);
+      if (ep.v_cache) ep.v_cache = (uint16_t*)((char*)ep.v_cache + (size_t)m0 * ep.kv_stream_stride * kv_esz);
       if (ep.argmax) ep.argmax += (size_t)m0 * TI_ARGMAX_SLOTS;
       if (m0 + mm < M) ep.step_ctr = nullptr;
       const int rc = gemm_impl(tiles, scales, bits | TI_BITS_G32 | (aff ? TI_BITS_AFF : 0),

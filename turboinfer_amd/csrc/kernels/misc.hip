@@ -216,13 +216,18 @@ __global__ void fill_uniform_f32_kernel(uint64_t stream, uint64_t n, float mul, 
 
 // Synthetic KV (or_model_fill_kv): slot p of kv-head kvh, dim d takes element
 // p*(kv_heads*hd) + kvh*hd + d of the oracle's [pos][kv*hd] stream.
-__global__ void fill_kv_kernel(uint64_t stream, int n, int kv_heads, int hd, int max_seq, uint16_t* dst) {
+// F8: an e4m3 cache (TI_BITS_KV8) takes the e4m3 of that fp16 value.
+template <bool F8>
+__global__ void fill_kv_kernel(uint64_t stream, int n, int kv_heads, int hd, int max_seq, void* dst) {
   const int64_t total = (int64_t)n * kv_heads * hd;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int p = (int)(i / (kv_heads * hd));
     const int c = (int)(i - (int64_t)p * kv_heads * hd);
     const int kvh = c / hd, d = c - kvh * hd;
-    dst[((size_t)kvh * max_seq + p) * hd + d] = f2h_soft(synth_unit(stream, (uint64_t)i));
+    const uint16_t h = f2h_soft(synth_unit(stream, (uint64_t)i));
+    const size_t at = ((size_t)kvh * max_seq + p) * hd + d;
+    if constexpr (F8) ((uint8_t*)dst)[at] = f2e4m3(h2f(h));
+    else ((uint16_t*)dst)[at] = h;
   }
 }
 
@@ -321,18 +326,29 @@ extern "C" int ti_fill_uniform_f16(uint64_t seed, uint32_t tensor_id, uint64_t n
   return TI_OK;
 }
 
-extern "C" int ti_fill_kv_uniform(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim,
-                                  int max_seq, uint16_t* dst, ti_stream_t stream) {
+template <bool F8>
+static int fill_kv_impl(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim, int max_seq, void* dst,
+                        ti_stream_t stream) {
   using namespace ti;
   if (!dst || n < 0 || n > max_seq || kv_heads < 1 || head_dim < 1)
     return ti_set_error(TI_ERR_ARG, "ti_fill_kv_uniform: bad arguments");
   if (n == 0) return TI_OK;
   const int64_t total = (int64_t)n * kv_heads * head_dim;
   const unsigned blocks = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-  hipLaunchKernelGGL(fill_kv_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, synth_stream(seed, tensor_id),
+  hipLaunchKernelGGL(fill_kv_kernel<F8>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, synth_stream(seed, tensor_id),
                      n, kv_heads, head_dim, max_seq, dst);
   TI_LAUNCH_CHECK("fill_kv_kernel");
   return TI_OK;
+}
+
+extern "C" int ti_fill_kv_uniform(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim,
+                                  int max_seq, uint16_t* dst, ti_stream_t stream) {
+  return fill_kv_impl<false>(seed, tensor_id, n, kv_heads, head_dim, max_seq, dst, stream);
+}
+
+extern "C" int ti_fill_kv_uniform_f8(uint64_t seed, uint32_t tensor_id, int n, int kv_heads, int head_dim,
+                                     int max_seq, uint8_t* dst, ti_stream_t stream) {
+  return fill_kv_impl<true>(seed, tensor_id, n, kv_heads, head_dim, max_seq, dst, stream);
 }
 
 extern "C" int ti_fill_uniform_f32(uint64_t seed, uint32_t tensor_id, uint64_t n, float mul, float add, float* dst,
