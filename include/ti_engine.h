@@ -31,9 +31,9 @@ typedef struct ti_engine_config {
   float eps;               /* rms_norm eps, reference default 1e-5 (tensor_engine.hpp:185) */
   int32_t bits;            /* weight format: 4 (INT4 g128), 8 (INT8 g128), 16 (fp16); | TI_BITS_KV8
                               (ti_hip.h): K / V kept as e4m3 bytes, half the cache memory -- the
-                              one-stream fused QKV + attention launch is then off and prompt
-                              chunks attend through the decode kernel; not with
-                              compat (TI_ERR_ARG) */
+                              one-stream fused QKV + attention launch is then off; prompt chunks
+                              attend through ti_attn_prefill_f8 where an fp16-cache engine takes
+                              ti_attn_prefill; not with compat (TI_ERR_ARG) */
   int32_t max_seq;         /* KV slots per stream */
   int32_t max_batch;       /* decode streams held by the engine */
   int32_t compat;          /* 1 = reference_compat: placeholder embeddings, attention
@@ -170,6 +170,14 @@ int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int 
  * rms_norm + lm_head on that row (env TI_PREFILL_LOGITS=0: a decode step instead).
  * Default: TI_GEMM_MAX_ROWS (int4) or 16; 0 = off. */
 int ti_engine_set_prefill(ti_engine* e, int rows);
+/* The attention entry point (ti_hip.h) a prompt chunk of `rows` rows takes on this engine, as a label
+ * in the style of ti_gemm_kernel_name: "ti_attn_prefill" / "ti_attn_prefill_f8" (row-major chunks: up
+ * to 16 rows, and more than 64 on int4 engines), "ti_attn_decode_packed" / "ti_attn_decode_packed_f8"
+ * (packed chunks: int4, 17-64 rows), "ti_attn_decode" / "ti_attn_decode_f8" (row-major chunks under
+ * env TI_ATTN_PREFILL=0); the _f8 names on a TI_BITS_KV8 engine.  Decided by the predicates the
+ * prefill itself launches by.  TI_ERR_ARG: null e / buf, rows < 1, len < 1; TI_ERR_UNSUPPORTED: a
+ * compat engine. */
+int ti_engine_prefill_attn_name(ti_engine* e, int rows, char* buf, int len);
 
 /* Fused hand-offs of single-stream steps: (1) the folded rms_norm (ti_hip.h TI_X_F16_FOLDED):
  * the epilogue that updates the residual also writes fp16(h * next norm weight) and

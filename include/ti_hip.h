@@ -120,7 +120,8 @@ int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_src, int N_
  * format itself: ti_wpack_* and ti_gemm_wq_a16 do not take it).  K / V are kept as OCP e4m3fn bytes
  * without a scale: byte = round-to-nearest-even e4m3 of min(max(x, -448), 448), converted from the
  * fp32 value the QKV epilogue holds; layout and strides unchanged in elements (ti_epilogue.kv_fp8,
- * ti_attn_decode_f8). */
+ * ti_attn_decode_f8 for decode steps and packed prompt chunks, ti_attn_prefill_f8 for row-major prompt
+ * chunks). */
 #define TI_BITS_KV8 128
 /* q uint8 [K][N_src] (0..15), d and m fp16 [K/32][N_src]: weight(k, c) = d * q + m. */
 int ti_wpack_q1_host(const uint8_t* q, const uint16_t* d, const uint16_t* m, int K, int N_src, int N_total, int row_map,
@@ -390,7 +391,16 @@ int ti_qkv_attn_supported(int bits, int K, int heads, int kv_heads, int head_dim
 int ti_attn_prefill(const float* q, const uint16_t* k_cache, const uint16_t* v_cache, int max_seq,
                     const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
                     ti_stream_t s);
-/* Kernel choice of later ti_attn_prefill calls in this process (parity tests and A/Bs; not a
+/* ti_attn_prefill over an e4m3 cache (TI_BITS_KV8; [kv_heads][max_seq][head_dim] bytes, max_seq and
+ * pos in elements as in ti_attn_decode_f8): the same arguments, limits, kernel choice and argument
+ * errors.  Every K / V byte is widened exactly to the fp16 operand the fp16 kernels' MFMA chains take
+ * (each finite e4m3 value is an fp16 value; NaN codes unspecified); q and p stay fp32 in fp16 hi + lo,
+ * so row m attends keys [0, pos[m]] as stored, its own included -- the function
+ * ti_attn_decode_f8(kv_stream_stride = 0) computes, reading the prefix once per 16 rows. */
+int ti_attn_prefill_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_seq,
+                       const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
+                       ti_stream_t s);
+/* Kernel choice of later ti_attn_prefill and ti_attn_prefill_f8 calls in this process (parity tests and A/Bs; not a
  * reference interface): 0 automatic (the default, TI_PF_WG applies), 1 the per-wave kernel,
  * 2 the shared-K/V kernel with 4-wave workgroups, 3 with 8-wave workgroups (key-split halves).
  * Modes 2 and 3 apply at head_dim 128 at any grid size; other head_dims take the per-wave kernel.

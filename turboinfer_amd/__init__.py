@@ -93,6 +93,7 @@ EXPORTED = [
     "ti_qkv_attn_xchg_bytes", "ti_qkv_attn_supported", "ti_qkv_attn_error_offset",
     "ti_logprob_rows", "ti_engine_score",
     "ti_attn_decode_f8", "ti_attn_decode_packed_f8", "ti_attn_decode_partials_f8", "ti_fill_kv_uniform_f8",
+    "ti_attn_prefill_f8", "ti_engine_prefill_attn_name",
     "ti_engine_read_kv",
 ]
 
@@ -214,6 +215,9 @@ def lib() -> C.CDLL:
                 getattr(L, n).argtypes = [vp, vp, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
             L.ti_fill_kv_uniform_f8.argtypes = [u64, C.c_uint32, i32, i32, i32, i32, vp, vp]
             L.ti_engine_read_kv.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+        if hasattr(L, "ti_attn_prefill_f8"):   # (older TI_LIB builds in A/B runs lack the e4m3 prefill attention)
+            L.ti_attn_prefill_f8.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]
+            L.ti_engine_prefill_attn_name.argtypes = [vp, i32, C.c_char_p, i32]
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]
@@ -424,6 +428,13 @@ class Engine:
         out = np.empty((self.cfg.kv_heads, n, self.cfg.head_dim), np.uint8 if kv8 else np.float16)
         check(lib().ti_engine_read_kv(self.h, layer, stream, which, pos0, n, _ptr(out)))
         return out
+
+    def prefill_attn_name(self, rows) -> str:
+        """ti_engine_prefill_attn_name: the attention entry point a prompt chunk of `rows` rows takes on this
+        engine, e.g. "ti_attn_prefill_f8" or "ti_attn_decode_packed"."""
+        buf = C.create_string_buffer(64)
+        check(lib().ti_engine_prefill_attn_name(self.h, rows, buf, 64))
+        return buf.value.decode()
 
     def generate(self, prompts, max_new, start_pos=None, want_logits=False):
         n = len(prompts)

@@ -17,6 +17,7 @@
 #include <atomic>
 #include <cmath>
 #include <queue>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -593,11 +594,10 @@ static bool prefill_attn_on();
 
 // Decode-attention workspace: the largest need over the row counts that run the split kernel --
 // decode batches up to max_batch and prompt chunks of up to 64 rows (ti_gemm_packed_rows; longer
-// chunks run ti_attn_prefill, no workspace), all chunk sizes when TI_ATTN_PREFILL=0.
+// chunks run ti_attn_prefill / ti_attn_prefill_f8, no workspace), all chunk sizes when TI_ATTN_PREFILL=0.
 size_t ws_bytes(const ti_engine* e) {
   const ti_engine_config& c = e->c;
-  // (TI_BITS_KV8: every prompt chunk runs the split kernel)
-  const int R = prefill_attn_on() && !e->kv8 ? std::min(e->rows_cap, std::max(c.max_batch, 64)) : e->rows_cap;
+  const int R = prefill_attn_on() ? std::min(e->rows_cap, std::max(c.max_batch, 64)) : e->rows_cap;
   size_t b = 0;
   for (int M = 1; M <= R; ++M) b = std::max(b, ti_attn_workspace_bytes(M, c.heads, c.head_dim, e->splits_for(M)));
   return b;
@@ -618,6 +618,16 @@ static bool prefill_attn_on() {
     return v ? atoi(v) != 0 : 1;
   }();
   return on != 0;
+}
+
+// The attention of a prompt chunk of `rows` rows: row-major chunks take one pass over the prefix per 16
+// rows on MFMA (ti_attn_prefill, ti_attn_prefill_f8 over an e4m3 cache), packed chunks (int4, 17-64
+// rows) and TI_ATTN_PREFILL=0 the decode kernel at stride 0.  enqueue_prefill launches by it and
+// ti_engine_prefill_attn_name labels by it.
+enum PfAttn { PF_ATTN_MFMA = 0, PF_ATTN_DECODE = 1, PF_ATTN_DECODE_PACKED = 2 };
+PfAttn prefill_attn_route(const ti_engine* e, int rows) {
+  if (packed_rows(e, rows)) return PF_ATTN_DECODE_PACKED;
+  return prefill_attn_on() ? PF_ATTN_MFMA : PF_ATTN_DECODE;
 }
 
 int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
@@ -662,10 +672,14 @@ int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
     ep.v_cache = vc;
     ep.kv_stream_stride = 0;
     TI_TRY(gemm_rows(e, L.qkv, rows, e->h, TI_X_F32_RMSNORM, H, L.attn_norm, ep, 4, false));
-    const bool pk = packed_rows(e, rows);
-    // (an e4m3 cache: the decode kernel at stride 0 -- every row reads its keys, its own included, from
-    // the quantised cache, as a decode step would; ti_attn_prefill reads fp16 only)
-    if (!pk && prefill_attn_on() && !e->kv8)   // row-major chunk: one pass over the prefix per 16 rows (MFMA)
+    const PfAttn route = prefill_attn_route(e, rows);
+    const bool pk = route == PF_ATTN_DECODE_PACKED;
+    // (an e4m3 cache: on either route every row reads its keys, its own included, from the quantised
+    // cache, as a decode step would)
+    if (route == PF_ATTN_MFMA && e->kv8)
+      TI_TRY(ti_attn_prefill_f8(e->q, reinterpret_cast<const uint8_t*>(kc), reinterpret_cast<const uint8_t*>(vc), c.max_seq,
+                                e->pos, rows, c.heads, c.kv_heads, c.head_dim, e->attn, e->s));
+    else if (route == PF_ATTN_MFMA)
       TI_TRY(ti_attn_prefill(e->q, kc, vc, c.max_seq, e->pos, rows, c.heads, c.kv_heads, c.head_dim, e->attn, e->s));
     else
       TI_TRY(attn_merged(e, pk, kc, vc, 0, rows, e->splits_for(rows)));
@@ -1579,6 +1593,16 @@ int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_c
   if (!e) return ti_set_error(TI_ERR_ARG, "ti_engine_counters: null");
   if (decode_steps) *decode_steps = e->n_decode_steps;
   if (prefill_chunks) *prefill_chunks = e->n_prefill_chunks;
+  return TI_OK;
+}
+
+int ti_engine_prefill_attn_name(ti_engine* e, int rows, char* buf, int len) {
+  if (!e || !buf || rows < 1 || len < 1) return ti_set_error(TI_ERR_ARG, "ti_engine_prefill_attn_name: null engine / buffer, rows or len < 1");
+  if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_prefill_attn_name: compat engine");
+  static const char* const names[3][2] = {{"ti_attn_prefill", "ti_attn_prefill_f8"},
+                                          {"ti_attn_decode", "ti_attn_decode_f8"},
+                                          {"ti_attn_decode_packed", "ti_attn_decode_packed_f8"}};
+  snprintf(buf, (size_t)len, "%s", names[prefill_attn_route(e, rows)][e->kv8 ? 1 : 0]);
   return TI_OK;
 }
 

@@ -67,6 +67,35 @@ __device__ __forceinline__ void e4m3x4_to_f32(uint32_t w, float& f0, float& f1, 
   const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
   f0 = lo[0]; f1 = lo[1]; f2 = hi[0]; f3 = hi[1];
 }
+// the 4 e4m3 bytes of w -> 4 fp16, packed in byte order (lo: bytes 0, 1; hi: bytes 2, 3), exactly: every
+// finite e4m3 value (subnormals 2^-9 .. 7 * 2^-9 included) is a normal fp16 value or zero, so
+// no conversion rounds: gfx950's direct v_cvt_scalef32_pk_f16_fp8 at scale 1 (one instruction per two
+// elements), or with TI_E4M3_F16_DIRECT=0 v_cvt_pk_f32_fp8 followed by the round-toward-zero pack (two).
+// NaN codes: unspecified.
+#ifndef TI_E4M3_F16_DIRECT
+#define TI_E4M3_F16_DIRECT 1
+#endif
+__device__ __forceinline__ void e4m3x4_to_f16x4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+#if TI_E4M3_F16_DIRECT
+  lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w, 1.0f, false));
+  hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w, 1.0f, true));
+#else
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a[0], a[1]));
+  hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(b[0], b[1]));
+#endif
+}
+// 8 bytes (w0: elements 0-3, w1: 4-7) -> the f16x8 MFMA fragment of the same 8 elements
+__device__ __forceinline__ f16x8 e4m3x8_to_f16x8(uint32_t w0, uint32_t w1) {
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t o;
+  uint32_t a, b;
+  e4m3x4_to_f16x4(w0, a, b);
+  o[0] = a; o[1] = b;
+  e4m3x4_to_f16x4(w1, a, b);
+  o[2] = a; o[3] = b;
+  return __builtin_bit_cast(f16x8, o);
+}
 
 // ------------------------------------------------------------ wave reductions
 template <int WIDTH>

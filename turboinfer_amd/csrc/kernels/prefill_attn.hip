@@ -23,6 +23,10 @@
 // So every accumulator row of a lane belongs to the lane's own column: each block's alpha rescales
 // it in place, and the lane writes hd/4 contiguous outputs of its column at the end.
 // Queries are dealt longest-prefix first; a 4-block K / V ring per wave hides the loads.
+//
+// The same kernels read an e4m3 cache (template parameter KV8, ti_attn_prefill_f8): every finite e4m3
+// value is an fp16 value, so each K / V byte is widened exactly to the fp16 operand above and only the
+// loads, the LDS image and the unpack differ (PfRaw<hd, true> and the KV8 note at the shared kernel).
 #include <math.h>
 #include <stdlib.h>
 
@@ -33,21 +37,48 @@
 namespace ti {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-template <int HD>
+template <int HD, bool KV8 = false>
 struct PfRaw;   // one lane's 16 (K) / hd/16 (V) fp16 values
 template <>
-struct PfRaw<128> {
+struct PfRaw<128, false> {
   using K = u32x4[4];   // 32 dims
   using V = u32x4;      // 8 dims
+  using T = uint16_t;
 };
 template <>
-struct PfRaw<64> {
+struct PfRaw<64, false> {
   using K = u32x4[2];   // 16 dims
   using V = uint2;      // 4 dims
+  using T = uint16_t;
+};
+// e4m3 cache (KV8): the same dims per lane in half the bytes.  A lane's K dims are CONTIGUOUS here --
+// step c of lane group g takes dims (hd / 4) g + 8 c + e, in the K and the Q fragment alike -- so the
+// row's hd / 4 bytes are one (hd 64) or two (hd 128) 16-byte loads, as wide as the fp16 kernel's.
+template <>
+struct PfRaw<128, true> {
+  using K = u32x4[2];   // 32 dims
+  using V = uint2;      // 8 dims
+  using T = uint8_t;
+};
+template <>
+struct PfRaw<64, true> {
+  using K = u32x4[1];   // 16 dims
+  using V = uint32_t;   // 4 dims
+  using T = uint8_t;
 };
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// 8 bytes at the LDS byte address a
+__device__ __forceinline__ u32x2 lds_read_b64(uint32_t a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const __attribute__((address_space(3))) u32x2*)a;
+#else
+  return u32x2{a, a};
+#endif
+}
 
 // fp32 x -> (hi, lo) fp16 with hi + lo = x to ~2^-22 relative
 __device__ __forceinline__ void pf_split(float x, _Float16& hi, _Float16& lo) {
@@ -65,19 +96,26 @@ __device__ __forceinline__ void pf_split(float x, _Float16& hi, _Float16& lo) {
 #ifndef TI_PF_RING
 #define TI_PF_RING 3   // K / V blocks in flight per wave (3: two waves per SIMD, held to 256 registers)
 #endif
+#ifndef TI_PF_F8_LOAD16
+#define TI_PF_F8_LOAD16 1   // per-wave e4m3 kernels: 1 a lane's K dims contiguous, 16-byte loads; 0 the fp16 kernels'
+                            // dims (32c + 8g + e) in 8-byte loads (the baseline, profiles/kv8_prefill_ab.txt)
+#endif
 #ifndef TI_PF_RING_DEEP
 #define TI_PF_RING_DEEP 4   // the ring when every wave of the launch has a SIMD to itself (4 and 6 measured equal)
 #endif
 
 // WPE: waves per SIMD the shallow-ring build must fit (2: at most 256 registers with the AGPRs)
-template <int HD, int RING = TI_PF_RING, int WPE = 1>
-__global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __restrict__ q, const uint16_t* __restrict__ kc,
-                                                          const uint16_t* __restrict__ vc, int max_seq,
+// KV8: the cache holds e4m3 bytes (ti_attn_prefill_f8); each K / V byte is widened exactly to the fp16
+// operand (e4m3x4_to_f16x4) right before its MFMA, everything after that is the fp16 instance's code
+template <int HD, int RING = TI_PF_RING, int WPE = 1, bool KV8 = false, typename KT = typename PfRaw<HD, KV8>::T>
+__global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __restrict__ q, const KT* __restrict__ kc,
+                                                          const KT* __restrict__ vc, int max_seq,
                                                           const int32_t* __restrict__ pos, int M, int heads, int gsh,
                                                           float scale, uint16_t* __restrict__ out) {
   constexpr int DV = HD / 16, KW = HD / 32;   // K: one 32-dim MFMA step per u32x4
-  using KRaw = typename PfRaw<HD>::K;
-  using VRaw = typename PfRaw<HD>::V;
+  constexpr int KN = KV8 ? KW / 2 : KW;       // u32x4 per lane and K row (e4m3: two steps per u32x4)
+  using KRaw = typename PfRaw<HD, KV8>::K;
+  using VRaw = typename PfRaw<HD, KV8>::V;
   const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
   // GQA: the 16 columns are (16 / G) rows x the G q-heads of kv-head blockIdx.y (column c: row
   // c >> gsh, head c & (G - 1)), so each K / V block serves the whole group
@@ -92,12 +130,15 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
     kmin = min(kmin, __shfl_xor(kmin, o, 64));
   }
   // B operand of step c: dims 32c + 8g + e of this lane's column, split into fp16 hi + lo
+  // (e4m3: dims (hd / 4) g + 8c + e, the K fragment's)
+  constexpr bool K16 = KV8 && TI_PF_F8_LOAD16;
+  constexpr int QG = K16 ? HD / 4 : 8, QC = K16 ? 8 : 32;
   f16x8 qh[KW], ql[KW];
   {
-    const float* qr = q + ((size_t)qi * heads + h) * HD + 8 * g;
+    const float* qr = q + ((size_t)qi * heads + h) * HD + QG * g;
 #pragma unroll
     for (int c = 0; c < KW; ++c) {
-      const float4 t0 = *(const float4*)(qr + 32 * c), t1 = *(const float4*)(qr + 32 * c + 4);
+      const float4 t0 = *(const float4*)(qr + QC * c), t1 = *(const float4*)(qr + QC * c + 4);
       const float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -121,6 +162,26 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
     kb = 0;
 #endif
     const int kk = min(kb * 16 + r, kl);
+    if constexpr (KV8) {   // byte offsets = element offsets
+      if constexpr (K16) {
+#pragma unroll
+        for (int c = 0; c < KN; ++c)
+          k[c] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, kk * HD + (HD / 4) * g + 16 * c, 0, 0));
+      } else {
+#pragma unroll
+        for (int c = 0; c < KW; ++c) {
+          const u32x2 t = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(krs, kk * HD + 8 * g + 32 * c, 0, 0));
+          k[c >> 1][2 * (c & 1)] = t[0];
+          k[c >> 1][2 * (c & 1) + 1] = t[1];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int off = min(kb * 16 + 4 * g + j, kl) * HD + r * DV;
+        if constexpr (HD == 128) v[j] = __builtin_bit_cast(VRaw, __builtin_amdgcn_raw_buffer_load_b64(vrs, off, 0, 0));
+        else v[j] = __builtin_bit_cast(VRaw, __builtin_amdgcn_raw_buffer_load_b32(vrs, off, 0, 0));
+      }
+    } else {
 #pragma unroll
     for (int c = 0; c < KW; ++c)
       k[c] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, (kk * HD + 8 * g + 32 * c) * 2, 0, 0));
@@ -129,6 +190,7 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
       const int off = (min(kb * 16 + 4 * g + j, kl) * HD + r * DV) * 2;
       if constexpr (HD == 128) v[j] = __builtin_bit_cast(VRaw, __builtin_amdgcn_raw_buffer_load_b128(vrs, off, 0, 0));
       else v[j] = __builtin_bit_cast(VRaw, __builtin_amdgcn_raw_buffer_load_b64(vrs, off, 0, 0));
+    }
     }
   };
   f32x4 acc[DV];
@@ -167,7 +229,7 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int c = 0; c < KW; ++c) asm volatile("" : "+v"(kr[u + b][c]));
+        for (int c = 0; c < KN; ++c) asm volatile("" : "+v"(kr[u + b][c]));
 #if TI_PF_DIAG & 2   // diagnostic: the K / V stream alone (each slot waited for and refilled, no math)
       if constexpr (HD == 128) {
 #pragma unroll
@@ -186,7 +248,9 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
       for (int c = 0; c < KW; ++c)
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          const f16x8 kf = __builtin_bit_cast(f16x8, kr[u + b][c]);
+          f16x8 kf;
+          if constexpr (KV8) kf = e4m3x8_to_f16x8(kr[u + b][c >> 1][2 * (c & 1)], kr[u + b][c >> 1][2 * (c & 1) + 1]);
+          else kf = __builtin_bit_cast(f16x8, kr[u + b][c]);
           s[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qh[c], s[b], 0, 0, 0);
           s[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, ql[c], s[b], 0, 0, 0);
         }
@@ -253,7 +317,14 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
         uint32_t vw[4][DV / 2];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if constexpr (HD == 128) {
+          if constexpr (KV8) {   // the row's DV bytes -> the DV fp16 the fp16 instance loads
+            if constexpr (HD == 128) {
+              e4m3x4_to_f16x4(vr[u + b][j].x, vw[j][0], vw[j][1]);
+              e4m3x4_to_f16x4(vr[u + b][j].y, vw[j][2], vw[j][3]);
+            } else {
+              e4m3x4_to_f16x4(vr[u + b][j], vw[j][0], vw[j][1]);
+            }
+          } else if constexpr (HD == 128) {
             vw[j][0] = vr[u + b][j][0]; vw[j][1] = vr[u + b][j][1]; vw[j][2] = vr[u + b][j][2]; vw[j][3] = vr[u + b][j][3];
           } else {
             vw[j][0] = vr[u + b][j].x; vw[j][1] = vr[u + b][j].y;
@@ -324,19 +395,47 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
 #ifndef TI_PF_WG_RING2
 #define TI_PF_WG_RING2 8   // the same, 8-wave workgroups (4 blocks per iteration; 8 beat 12 and 16, profiles/r5_prefill_wg_ring_ab.txt)
 #endif
+#ifndef TI_PF_WG_RING_F8
+#define TI_PF_WG_RING_F8 6    // e4m3 cache: blocks in the LDS ring (4 KiB each, K + V), 4-wave workgroups (8: 5 % faster
+                              // at 512 rows, even elsewhere; never the automatic choice, profiles/kv8_prefill_ab.txt)
+#endif
+#ifndef TI_PF_WG_RING2_F8
+#define TI_PF_WG_RING2_F8 8   // the same, 8-wave workgroups: the fp16 depths in half the LDS (12 measured slower)
+#endif
 // HALVES 2: 8 waves, two per SIMD -- waves w and w + 4 share query block w & 3 and take alternate
 // pairs of its key blocks (iteration = 4 blocks, half h computes blocks 2 h, 2 h + 1 of it), merging
 // their (max, sum, O) through LDS at the end: two chains per SIMD hide each other's latencies.
-template <int HALVES, int R>
-__global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const float* __restrict__ q, const uint16_t* __restrict__ kc,
-                                                                 const uint16_t* __restrict__ vc, int max_seq,
+//
+// KV8 (e4m3 cache, ti_attn_prefill_f8): a K or V block is 16 keys x 128 B = 2 KiB, two 1 KiB DMA
+// instructions of 8 key rows each (lane l: row l >> 3, 16-byte chunk l & 7); an iteration's BI blocks are
+// 4 BI instructions, wave w issues two: both halves of K (w even) or V (w odd) of block w / 2, so
+// 2 (R / BI - 1) are in flight per wave and the counted wait is vmcnt(2 (R / BI - 2)).
+//   K block in LDS: [16 keys][8 chunks of 16 B], logical chunk c of key row r at physical
+//   c ^ ((r >> 1) & 5), applied to the DMA's source address and to the fragment read together.  Lane
+//   (r, g) reads its 32 contiguous dims (chunks 2g, 2g + 1: the per-wave e4m3 mapping) in two
+//   ds_read_b128.  Those are conflict-free: a ds_read_b128 lane group is rows {0-3, 12-15} of lane group
+//   g and rows {4-11} of g ^ 1 (or the reverse); rows r and r ^ 1 lie in opposite 128-byte halves of the
+//   256-byte bank row with the same swizzle, and within a half the first set reads chunks
+//   c ^ {0, 1, 4, 5} and the second (c ^ 2) ^ {0, 1, 4, 5} = c ^ {2, 3, 6, 7}: 16 lanes, 16 distinct
+//   16-byte slots.
+//   V block: [16 keys][128 B] with key rows 4-7 and 12-15 swapped pairwise (row k at k ^ ((k >> 2) & 1),
+//   again on the source address and the read): lane (r, g) reads the 8 bytes 8r .. 8r + 7 of rows
+//   4g + j with ds_read_b64, whose lane groups are the wave's halves -- g and g + 1 then read rows of
+//   opposite parity, the two 128-byte halves of the bank row, 16 lanes x 8 B each: conflict-free.
+// The halves' merge scratch (34 KiB) is larger than an 8-block e4m3 ring (32 KiB): the ring array then
+// gets RA > R slots, the extra ones being the merge's own storage.
+template <int HALVES, int R, bool KV8 = false, typename KT = typename PfRaw<128, KV8>::T>
+__global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const float* __restrict__ q, const KT* __restrict__ kc,
+                                                                 const KT* __restrict__ vc, int max_seq,
                                                                  const int32_t* __restrict__ pos, int M, int heads, int gsh,
                                                                  float scale, uint16_t* __restrict__ out) {
   constexpr int HD = 128, DV = HD / 16, KW = HD / 32, NB = 2, BI = NB * HALVES;   // BI: blocks per iteration
   static_assert(R % BI == 0 && R >= 2 * BI, "ring: whole iterations, one in flight beside the one computed");
   // K and V rings in ONE array: the halves' merge at the end reuses it as scratch (4 query blocks x
   // 64 lanes x (4 DV + 2) floats), which is larger than the K ring alone
-  __shared__ __attribute__((aligned(16))) uint16_t skv[2][R][16 * HD];
+  constexpr size_t kMerge = HALVES == 1 ? 0 : 4 * 64 * (4 * DV + 2) * sizeof(float), kSlot = 2 * 16 * HD * sizeof(KT);
+  constexpr int RA = R * kSlot >= kMerge ? R : (int)((kMerge + kSlot - 1) / kSlot);   // (fp16: RA = R)
+  __shared__ __attribute__((aligned(16))) KT skv[2][RA][16 * HD];
   static_assert(HALVES == 1 || 4 * 64 * (4 * DV + 2) * sizeof(float) <= sizeof(skv), "halves' merge scratch");
   auto& sk = skv[0];
   auto& sv = skv[1];
@@ -356,12 +455,13 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
     kmin = min(kmin, __shfl_xor(kmin, o, 64));
   }
   if (lane == 0 && half == 0) s_kmax[qw] = live ? kmax : 0;
+  constexpr int QL = KV8 ? HD / 4 : 8, QC = KV8 ? 8 : 32;   // e4m3: step c is dims 32 g + 8 c + e
   f16x8 qh[KW], ql[KW];
   {
-    const float* qr = q + ((size_t)qi * heads + h) * HD + 8 * g;
+    const float* qr = q + ((size_t)qi * heads + h) * HD + QL * g;
 #pragma unroll
     for (int c = 0; c < KW; ++c) {
-      const float4 t0 = *(const float4*)(qr + 32 * c), t1 = *(const float4*)(qr + 32 * c + 4);
+      const float4 t0 = *(const float4*)(qr + QC * c), t1 = *(const float4*)(qr + QC * c + 4);
       const float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -376,8 +476,8 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
   const int kmax_wg = max(max(s_kmax[0], s_kmax[1]), max(s_kmax[2], s_kmax[3]));
   const int kl = min(kmax_wg, max_seq - 1);   // rows past it may be unwritten: read row kl instead
   const int nkb = kmax_wg / 16 + 1, nkb_w = live ? kmax / 16 + 1 : 0;
-  const uint16_t* kbase = kc + (size_t)kvh * max_seq * HD;
-  const uint16_t* vbase = vc + (size_t)kvh * max_seq * HD;
+  const KT* kbase = kc + (size_t)kvh * max_seq * HD;
+  const KT* vbase = vc + (size_t)kvh * max_seq * HD;
   const uint32_t sk_lds = (uint32_t)(uintptr_t)&sk[0][0], sv_lds = (uint32_t)(uintptr_t)&sv[0][0];
   // An iteration's BI blocks are 8 BI DMA instructions of 1 KiB (a block: K rows 0-3, 4-7, 8-11, 12-15,
   // then V's); wave w issues instructions 4 w .. 4 w + 3: all of K or all of V of block w / 2.
@@ -387,12 +487,22 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
     if (kb0 >= R - BI) return;
 #endif
     const int kb = kb0 + dblk, slot = kb % R;
-    const uint32_t base = (dv ? sv_lds : sk_lds) + (uint32_t)(slot * 16 * HD * 2);
+    const uint32_t base = (dv ? sv_lds : sk_lds) + (uint32_t)(slot * 16 * HD * sizeof(KT));
+    if constexpr (KV8) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = 8 * i + (lane >> 3), ch = lane & 7;   // the LDS row and chunk this lane's 16 B land in
+        const int key = min(kb * 16 + (dv ? row ^ ((row >> 2) & 1) : row), kl);
+        const KT* src = (dv ? vbase : kbase) + (size_t)key * HD + (dv ? ch : ch ^ ((row >> 1) & 5)) * 16;
+        dma_1k_asm(src, __builtin_amdgcn_readfirstlane(base + (uint32_t)(i * 1024)));
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = 4 * i + (lane >> 4), key = min(kb * 16 + row, kl);
-      const uint16_t* src = dv ? vbase + (size_t)key * HD + dch * 8 : kbase + (size_t)key * HD + ((dch ^ row) * 8);
+      const KT* src = dv ? vbase + (size_t)key * HD + dch * 8 : kbase + (size_t)key * HD + ((dch ^ row) * 8);
       dma_1k_asm(src, __builtin_amdgcn_readfirstlane(base + (uint32_t)(i * 4 * HD * 2)));
+    }
     }
   };
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // q and pos in: only the DMAs are counted below
@@ -404,8 +514,9 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
   float m_run = -INFINITY, l_run = 0.0f;
   constexpr float kPfSlack = 8.0f;   // as above: O rescaled only when a column max moves by > 8
   for (int kbi = 0; kbi < nkb; kbi += BI) {
-    // this wave's 4 DMAs of iteration kbi are the oldest of the 4 (R / BI - 1) in flight
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (R / BI - 2)) : "memory");
+    // this wave's 4 DMAs of iteration kbi are the oldest of the 4 (R / BI - 1) in flight (e4m3: 2 per
+    // iteration, 2 (R / BI - 1) in flight)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((KV8 ? 2 : 4) * (R / BI - 2)) : "memory");
     __syncthreads();
 #if !TI_PF_WG_LATE_DMA
     issue(kbi + R - BI);
@@ -421,7 +532,33 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
     if (act) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        const uint16_t* kr = &sk[(kb + b) % R][r * HD];
+        const KT* kr = &sk[(kb + b) % R][r * HD];
+        if constexpr (KV8) {
+          const int sw = (r >> 1) & 5;
+          const u32x4 k0 = *(const u32x4*)(kr + ((2 * g) ^ sw) * 16), k1 = *(const u32x4*)(kr + ((2 * g + 1) ^ sw) * 16);
+          sacc[b] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+          for (int c = 0; c < KW; ++c) {
+            const u32x4 kk = c < 2 ? k0 : k1;
+            const f16x8 kf = e4m3x8_to_f16x8(kk[2 * (c & 1)], kk[2 * (c & 1) + 1]);
+            sacc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qh[c], sacc[b], 0, 0, 0);
+            sacc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, ql[c], sacc[b], 0, 0, 0);
+          }
+          const uint32_t vb = sv_lds + (uint32_t)(((kb + b) % R) * 16 * HD);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            // (each address through an empty asm: kept a ds_read_b64 each -- merged into ds_read2st64_b64
+            // pairs they would take the 32-bank path at a quarter of the rate)
+            uint32_t va = vb + (uint32_t)(((4 * g + j) ^ (g & 1)) * HD + r * DV);
+            asm volatile("" : "+v"(va));
+            const u32x2 v8 = lds_read_b64(va);
+            uint32_t w0, w1, w2, w3;
+            e4m3x4_to_f16x4(v8[0], w0, w1);
+            e4m3x4_to_f16x4(v8[1], w2, w3);
+            vraw[b][j] = (u32x4){w0, w1, w2, w3};
+          }
+          continue;
+        }
 #if TI_PF_QK_SPLIT   // the hi and lo products in two chains (four independent per step), summed after
         f32x4 sh = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}, sl = sh;
 #pragma unroll
@@ -440,7 +577,7 @@ __global__ __launch_bounds__(256 * HALVES, 1) void attn_prefill_wg_kernel(const 
           sacc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, ql[c], sacc[b], 0, 0, 0);
         }
 #endif
-        const uint16_t* vb = &sv[(kb + b) % R][0];
+        const KT* vb = &sv[(kb + b) % R][0];
 #pragma unroll
         for (int j = 0; j < 4; ++j) vraw[b][j] = *(const u32x4*)(vb + (4 * g + j) * HD + r * DV);
       }
@@ -574,17 +711,33 @@ extern "C" int ti_attn_prefill_set_kernel(int mode) {
   return g_pf_kernel.exchange(mode);
 }
 
-extern "C" int ti_attn_prefill(const float* q, const uint16_t* k_cache, const uint16_t* v_cache, int max_seq,
-                               const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
-                               ti_stream_t stream) {
-  if (!q || !k_cache || !v_cache || !pos || !out) return ti_set_error(TI_ERR_ARG, "ti_attn_prefill: null pointer");
+// SIMDs of the current device (4 per CU), -1 when it cannot be asked
+static int pf_simds() {
+  static std::atomic<int> simds{0};
+  int ns = simds.load(std::memory_order_relaxed);
+  if (ns == 0) {
+    int dev = 0, n = 0;
+    ns = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
+             ? 4 * n : -1;
+    simds.store(ns, std::memory_order_relaxed);   // (a racing first call stores the same value)
+  }
+  return ns;
+}
+
+// ti_attn_prefill (fp16 cache) and ti_attn_prefill_f8 (e4m3 cache): one set of checks and one kernel
+// choice.  The e4m3 instances keep the fp16 thresholds: at 512 rows of 7B the 8-wave shared-K/V kernel
+// measured 16.4-17.4 us against 18.7-19.7 us for the per-wave kernel, at 128 / 256 rows the per-wave
+// kernel runs either way (profiles/kv8_prefill_ab.txt).
+template <bool KV8, typename KT>
+static int pf_launch(const char* name, const float* q, const KT* k_cache, const KT* v_cache, int max_seq, const int32_t* pos,
+                     int M, int heads, int kv_heads, int head_dim, uint16_t* out, ti_stream_t stream) {
+  if (!q || !k_cache || !v_cache || !pos || !out) return ti_set_error(TI_ERR_ARG, "%s: null pointer", name);
   if (M < 1 || heads < 1 || kv_heads < 1 || heads % kv_heads || max_seq < 1 || M > 65535 * 16 || heads > 65535)
-    return ti_set_error(TI_ERR_ARG, "ti_attn_prefill: bad sizes M=%d heads=%d kv_heads=%d max_seq=%d", M, heads,
-                        kv_heads, max_seq);
+    return ti_set_error(TI_ERR_ARG, "%s: bad sizes M=%d heads=%d kv_heads=%d max_seq=%d", name, M, heads, kv_heads, max_seq);
   if (head_dim != 64 && head_dim != 128)
-    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_attn_prefill: head_dim %d not in {64,128}", head_dim);
+    return ti_set_error(TI_ERR_UNSUPPORTED, "%s: head_dim %d not in {64,128}", name, head_dim);
   const int G = heads / kv_heads;
-  if (G & (G - 1) || G > 16) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_attn_prefill: heads / kv_heads %d not a power of 2 <= 16", G);
+  if (G & (G - 1) || G > 16) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: heads / kv_heads %d not a power of 2 <= 16", name, G);
   const int gsh = __builtin_ctz(G), qpw = 16 >> gsh;
   const dim3 grid((M + qpw - 1) / qpw, kv_heads);
   const float scale = 1.0f / sqrtf((float)head_dim);   // tensor_engine.cpp:1288
@@ -594,14 +747,7 @@ extern "C" int ti_attn_prefill(const float* q, const uint16_t* k_cache, const ui
   // so each wave keeps the deep ring: the longest rows' waves set the time, and their key
   // stream is latency-bound (one block per ~1.1 us at 3 in flight).  Larger chunks keep the
   // 3-deep ring, two waves per SIMD.
-  static std::atomic<int> simds{0};
-  int ns = simds.load(std::memory_order_relaxed);
-  if (ns == 0) {
-    int dev = 0, n = 0;
-    ns = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
-             ? 4 * n : -1;
-    simds.store(ns, std::memory_order_relaxed);   // (a racing first call stores the same value)
-  }
+  const int ns = pf_simds();
   const bool deep = (long)grid.x * grid.y <= ns;
   static const int wgk = [] {   // 0: per-wave kernel, 1: workgroup of 4 waves, 2: of 8 (key-split halves)
     const char* e = getenv("TI_PF_WG");
@@ -611,30 +757,43 @@ extern "C" int ti_attn_prefill(const float* q, const uint16_t* k_cache, const ui
   const int k = forced == 0 ? wgk : forced - 1;
   const bool wg = k > 0, wg2 = k == 2;
   const dim3 gw((grid.x + 3) / 4, kv_heads);
+  constexpr int R1 = KV8 ? TI_PF_WG_RING_F8 : TI_PF_WG_RING, R2 = KV8 ? TI_PF_WG_RING2_F8 : TI_PF_WG_RING2;
   // 4 query blocks of a kv-head per workgroup, K / V shared in LDS -- when that still gives every CU
   // a workgroup (256 rows of 7B: 128 workgroups, the per-wave kernel's 512 waves are faster)
   if (head_dim == 128 && wg && (forced > 1 || (long)gw.x * gw.y * 4 >= ns)) {
     if (wg2)
-      hipLaunchKernelGGL((ti::attn_prefill_wg_kernel<2, TI_PF_WG_RING2>), gw, dim3(512), 0, s, q, k_cache, v_cache, max_seq,
+      hipLaunchKernelGGL((ti::attn_prefill_wg_kernel<2, R2, KV8>), gw, dim3(512), 0, s, q, k_cache, v_cache, max_seq,
                          pos, M, heads, gsh, scale, out);
     else
-      hipLaunchKernelGGL((ti::attn_prefill_wg_kernel<1, TI_PF_WG_RING>), gw, dim3(256), 0, s, q, k_cache, v_cache, max_seq,
+      hipLaunchKernelGGL((ti::attn_prefill_wg_kernel<1, R1, KV8>), gw, dim3(256), 0, s, q, k_cache, v_cache, max_seq,
                          pos, M, heads, gsh, scale, out);
   } else if (head_dim == 128) {
     if (deep)
-      hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING_DEEP>), grid, dim3(64), 0, s, q, k_cache, v_cache,
+      hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING_DEEP, 1, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache,
                          max_seq, pos, M, heads, gsh, scale, out);
     else
-      hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING, 2>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
+      hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING, 2, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
                          pos, M, heads, gsh, scale, out);
   } else {
     if (deep)
-      hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING_DEEP>), grid, dim3(64), 0, s, q, k_cache, v_cache,
+      hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING_DEEP, 1, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache,
                          max_seq, pos, M, heads, gsh, scale, out);
     else
-      hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING, 2>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
+      hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING, 2, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
                          pos, M, heads, gsh, scale, out);
   }
   TI_LAUNCH_CHECK("attn_prefill_kernel");
   return TI_OK;
+}
+
+extern "C" int ti_attn_prefill(const float* q, const uint16_t* k_cache, const uint16_t* v_cache, int max_seq,
+                               const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
+                               ti_stream_t stream) {
+  return pf_launch<false>("ti_attn_prefill", q, k_cache, v_cache, max_seq, pos, M, heads, kv_heads, head_dim, out, stream);
+}
+
+extern "C" int ti_attn_prefill_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_seq,
+                                  const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
+                                  ti_stream_t stream) {
+  return pf_launch<true>("ti_attn_prefill_f8", q, k_cache, v_cache, max_seq, pos, M, heads, kv_heads, head_dim, out, stream);
 }
