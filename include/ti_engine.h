@@ -162,6 +162,34 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
 int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int start_pos, const int32_t* targets,
                     float* out_logprob, int32_t* out_top1);
 
+/* Lookahead greedy decoding of ONE request in stream slot `stream` (no reference counterpart: the reference's
+ * generate() runs one forward pass per token, inference_engine.cpp:734-802).  Each verify step feeds the
+ * last token and up to k tokens drafted by an n-gram lookup in corpus ++ prompt ++ generated (ti_hip.h
+ * ti_lookahead_begin) as k + 1 rows of one prompt chunk -- weights read once, the attention by
+ * ti_attn_prefill_split -- and keeps the drafts the rows' greedy tokens confirm (ti_lookahead_accept): between
+ * 1 and k + 1 tokens of exactly the greedy sequence per step.  prompt[0 .. n - 2] run as prompt chunks,
+ * prompt[n - 1] is row 0 of the first step.  The step is one captured graph per (slot, k, splits), kept with
+ * the step graphs; it replays in chunks of 4, 8, 16, 32, then 64 with one small read-back of the device state
+ * after each, until done, at most max_new steps.  The k + 1 rows' logits and the history live in buffers
+ * allocated by the first call, outside what ti_engine_memory reports.  The verify step runs without the
+ * folded rms_norm and without the fused QKV + attention launch (both are one-row paths).
+ * corpus (host, [corpus_len], nullable with corpus_len 0): reference text the continuation may repeat.
+ * out_tokens (host, [max_new]): the greedy tokens, -1 after a stop token (ti_engine_set_stop applies; the
+ * stop token is included).  stats (nullable): verify steps run, drafts proposed, drafts accepted, tokens
+ * produced.  ti_engine_counters: decode_steps rises by the verify steps, prefill_chunks by the prompt chunks.
+ * On return the slot's KV rows [start_pos, start_pos + prompt_len + produced - 1) are what
+ * ti_engine_generate would have left; the next k rows are scratch (rejected drafts).  Generation continues
+ * from there with either entry point (the last produced token as prompt, start_pos + prompt_len + produced - 1).
+ * TI_ERR_ARG before anything is enqueued: null e / prompt / out_tokens, null corpus with corpus_len != 0,
+ * stream outside [0, max_batch), prompt_len < 1, max_new < 1, k outside [1, 15], ngram outside [1, 8],
+ * corpus_len < 0, a prompt or corpus token outside [0, vocab), start_pos < 0,
+ * start_pos + prompt_len + max_new - 1 + k > max_seq (the verify rows need k slots of head-room).
+ * TI_ERR_UNSUPPORTED: a compat engine, a TI_BITS_KV8 engine. */
+typedef struct ti_lookahead_stats { int32_t steps, drafted, accepted, produced; } ti_lookahead_stats;
+int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                                 const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
+                                 int32_t* out_tokens, ti_lookahead_stats* stats);
+
 /* Prefill of ti_engine_generate's prompts (reference forward_pass, inference_engine.cpp:
  * 1429-1491): all but the last token of the shortest prompt are processed `rows` tokens at a
  * time as rows of the batched GEMMs and causal attention over the stream's own KV cache,

@@ -400,6 +400,25 @@ int ti_attn_prefill(const float* q, const uint16_t* k_cache, const uint16_t* v_c
 int ti_attn_prefill_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_seq,
                        const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
                        ti_stream_t s);
+/* ti_attn_prefill for a SHORT chunk behind a long prefix (the verify step of lookahead decoding): the same
+ * function, contract and argument errors (fp16 cache of one stream, row m attends keys [0, pos[m]], any
+ * positions in [0, max_seq), head_dim 64 / 128, heads / kv_heads a power of two <= 16, fp32 q, fp16 out), with
+ * 1 <= M <= 16 and the prefix split over 1 <= splits <= 32 waves per (16 columns, kv-head): grid (query
+ * blocks, kv_heads, splits), every K / V block read once for all rows.  The split ranges are computed in the
+ * kernel from pos (blocks [0, min pos / 16] dealt evenly, the tail up to max pos / 16 to the last split; a
+ * split without blocks writes (-inf, 0, zeros)); each split leaves its unnormalised fp32 accumulators and
+ * (m, l) per column in the workspace and the last arriver of a (query block, kv-head) -- found by a ticket,
+ * after its stores have drained -- merges the splits in split order 0 .. splits - 1, so the result is
+ * bit-reproducible from run to run whatever the arrival order.  Arithmetic: the per-wave kernel's.
+ * workspace: ti_attn_prefill_split_workspace_bytes(M, heads, head_dim, splits) bytes (0 for arguments outside
+ * the limits) for the largest M and splits the caller will use, zeroed once by the owner; every call leaves
+ * its tickets re-armed.  One launch at a time per workspace (stream order), calls of one `heads`.
+ * M outside [1, 16], splits outside [1, 32], a null pointer: TI_ERR_ARG, nothing launched.  Graph-capturable
+ * (no host read of pos, no allocation). */
+size_t ti_attn_prefill_split_workspace_bytes(int M, int heads, int head_dim, int splits);
+int ti_attn_prefill_split(const float* q, const uint16_t* k_cache, const uint16_t* v_cache, int max_seq,
+                          const int32_t* pos, int M, int heads, int kv_heads, int head_dim, int splits,
+                          float* workspace, uint16_t* out, ti_stream_t s);
 /* Kernel choice of later ti_attn_prefill and ti_attn_prefill_f8 calls in this process (parity tests and A/Bs; not a
  * reference interface): 0 automatic (the default, TI_PF_WG applies), 1 the per-wave kernel,
  * 2 the shared-K/V kernel with 4-wave workgroups, 3 with 8-wave workgroups (key-split halves).
@@ -448,6 +467,46 @@ typedef struct ti_step_args {
   float* fold_ss;                    /* [M] */
 } ti_step_args;
 int ti_step_begin(const ti_step_args* a, ti_stream_t s);
+
+/* ------------------------------------------------------- lookahead greedy decoding (device bookkeeping)
+ * A verify step feeds R = k + 1 rows of ONE stream: the last token of the history and up to k drafted
+ * tokens, found by an n-gram lookup in the history itself; the rows' greedy tokens then say how many drafts
+ * were right.  The output is exactly the greedy sequence.  Both launches are graph-capturable: what changes
+ * between calls or steps is read from device memory.
+ *   state [TI_LA_STATE_WORDS] int32: 0 hist_len L, 1 pos (position of hist[L - 1], the token fed as row 0),
+ *         2 produced, 3 done, 4 steps, 5 drafted, 6 accepted, 7 nd (drafts of the current step)
+ *   cfg   [4] int32: 0 ngram (1 .. 8), 1 max_new, 2 stop token (-1 = none), 3 cap (elements of hist)
+ *   hist  [cap] int32 = corpus ++ prompt ++ generated
+ * ti_lookahead_begin (one workgroup per row; the head of the step, in ti_step_begin's place).  Drafts allowed
+ * Keff = min(k, max_new - produced - 1).  For g from min(ngram, L - 1) down to 1, the largest i <= L - g - 1
+ * with hist[i .. i + g) == hist[L - g .. L) gives the drafts hist[i + g .. min(i + g + Keff, L)): the longest
+ * suffix wins, then the most recent match; no match (or Keff < 1): nd = 0.  Row j gets row_tok[j] = hist[L - 1]
+ * (row 0 and the padding rows) or draft j (1 <= j <= nd), pos[j] = min(state pos + j, max_pos), the fp16
+ * embedding row of its token as fp32 in h[j], and zeroed argmax keys; state[7] = nd.  With done set: row 0 /
+ * padding only, the state untouched (the rest of a step then runs harmlessly).
+ * ti_lookahead_accept (after the lm_head's TI_EPI_LOGITS_ARGMAX over the R rows): g_j = row j's greedy token,
+ * a = the number of leading j < nd with row_tok[j + 1] == g_j; emits g_0 .. g_a, cut after the first stop
+ * token (included) and at max_new, into hist[L ..] and out_tokens[produced ..]; hist_len, pos and produced
+ * advance by the number emitted n, steps by 1, drafted by nd, accepted by min(n, a); done = 1 on a stop token
+ * or at max_new.  With done set on entry: nothing.
+ * TI_ERR_ARG (nothing launched): a null pointer, k outside [1, 15], hidden < 1, vocab < 1, max_pos < 0. */
+#define TI_LA_STATE_WORDS 8
+#define TI_LA_MAX_K 15
+#define TI_LA_MAX_NGRAM 8
+typedef struct ti_lookahead_args {
+  int32_t* state;                    /* [TI_LA_STATE_WORDS] */
+  const int32_t* cfg;                /* [4] */
+  int32_t* hist;                     /* [cap] */
+  int32_t k, hidden, vocab, max_pos; /* max_pos: the slot's last KV row (max_seq - 1) */
+  const uint16_t* emb;               /* [vocab][hidden] fp16 */
+  float* h;                          /* [k + 1][hidden] */
+  int32_t* row_tok;                  /* [k + 1] */
+  int32_t* pos;                      /* [k + 1] */
+  unsigned long long* argmax;        /* [k + 1][TI_ARGMAX_SLOTS] */
+  int32_t* out_tokens;               /* [max_new] */
+} ti_lookahead_args;
+int ti_lookahead_begin(const ti_lookahead_args* a, ti_stream_t s);
+int ti_lookahead_accept(const ti_lookahead_args* a, ti_stream_t s);
 
 /* ------------------------------------------------------- on-device sampling
  * InferenceEngine::sample_next_token (inference_engine.cpp:1554-1673) per stream, the uniform

@@ -60,6 +60,19 @@ class StepArgs(C.Structure):
                 ("fold_x", C.c_void_p), ("fold_ss", C.c_void_p)]
 
 
+class LookaheadArgs(C.Structure):
+    """ti_lookahead_args (include/ti_hip.h)."""
+    _fields_ = [("state", C.c_void_p), ("cfg", C.c_void_p), ("hist", C.c_void_p), ("k", C.c_int32),
+                ("hidden", C.c_int32), ("vocab", C.c_int32), ("max_pos", C.c_int32), ("emb", C.c_void_p),
+                ("h", C.c_void_p), ("row_tok", C.c_void_p), ("pos", C.c_void_p), ("argmax", C.c_void_p),
+                ("out_tokens", C.c_void_p)]
+
+
+class LookaheadStats(C.Structure):
+    """ti_lookahead_stats (include/ti_engine.h)."""
+    _fields_ = [("steps", C.c_int32), ("drafted", C.c_int32), ("accepted", C.c_int32), ("produced", C.c_int32)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("inter", C.c_int32),
@@ -95,6 +108,8 @@ EXPORTED = [
     "ti_attn_decode_f8", "ti_attn_decode_packed_f8", "ti_attn_decode_partials_f8", "ti_fill_kv_uniform_f8",
     "ti_attn_prefill_f8", "ti_engine_prefill_attn_name",
     "ti_engine_read_kv",
+    "ti_attn_prefill_split", "ti_attn_prefill_split_workspace_bytes", "ti_lookahead_begin", "ti_lookahead_accept",
+    "ti_engine_generate_lookahead",
 ]
 
 _lib = None
@@ -218,6 +233,14 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_attn_prefill_f8"):   # (older TI_LIB builds in A/B runs lack the e4m3 prefill attention)
             L.ti_attn_prefill_f8.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]
             L.ti_engine_prefill_attn_name.argtypes = [vp, i32, C.c_char_p, i32]
+        if hasattr(L, "ti_engine_generate_lookahead"):   # (older TI_LIB builds in A/B runs lack lookahead decoding)
+            L.ti_attn_prefill_split.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+            L.ti_attn_prefill_split_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            L.ti_attn_prefill_split_workspace_bytes.restype = sz
+            L.ti_lookahead_begin.argtypes = [C.POINTER(LookaheadArgs), vp]
+            L.ti_lookahead_accept.argtypes = [C.POINTER(LookaheadArgs), vp]
+            L.ti_engine_generate_lookahead.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp,
+                                                       C.POINTER(LookaheadStats)]
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]
@@ -463,6 +486,18 @@ class Engine:
         check(lib().ti_engine_score(self.h, stream, _ptr(t), t.size, start_pos, None if tg is None else _ptr(tg),
                                     _ptr(lp), None if top1 is None else _ptr(top1)))
         return (lp, top1) if want_top1 else lp
+
+    def generate_lookahead(self, prompt, max_new, k=7, ngram=3, corpus=None, stream=0, start_pos=0):
+        """ti_engine_generate_lookahead: greedy tokens of one request, k n-gram drafts verified per step ->
+        (tokens [max_new], -1 after a stop token; stats dict: steps, drafted, accepted, produced)."""
+        p = np.ascontiguousarray(prompt, np.int32).reshape(-1)
+        cp = None if corpus is None else np.ascontiguousarray(corpus, np.int32).reshape(-1)
+        out = np.zeros(max(int(max_new), 1), np.int32)
+        st = LookaheadStats()
+        check(lib().ti_engine_generate_lookahead(self.h, stream, _ptr(p), p.size, start_pos,
+                                                 None if cp is None or cp.size == 0 else _ptr(cp),
+                                                 0 if cp is None else cp.size, k, ngram, max_new, _ptr(out), C.byref(st)))
+        return out, dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted, produced=st.produced)
 
     def generate_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, start_pos=None):
         """ti_engine_generate_sampled: tokens [n][max_new] and log-probs [n][max_new]."""

@@ -51,6 +51,15 @@ int kv_bits_option(const ModelMetadata& md) {
   return b;
 }
 
+// "turboinfer.lookahead" / TI_LOOKAHEAD: n-gram drafts verified per step by a greedy request that runs alone
+// (ti_engine_generate_lookahead); 0 (the default) = off, up to 15; not with the e4m3 KV cache.
+int lookahead_option(const ModelMetadata& md, int kv_bits) {
+  const int k = engine_option(md, "turboinfer.lookahead", "TI_LOOKAHEAD", 0);
+  if (k < 0 || k > TI_LA_MAX_K) throw std::runtime_error("InferenceEngine: lookahead must be 0 (off) .. 15 drafts per step");
+  if (k > 0 && kv_bits == 8) throw std::runtime_error("InferenceEngine: lookahead needs the fp16 KV cache (kv_bits 16)");
+  return k;
+}
+
 [[noreturn]] void off_path(const std::string& what, const char* row) {
   throw std::runtime_error("InferenceEngine::" + what + ": not part of the MI355X decode hot path (SURVEY.md 8(f) " +
                            row + ")");
@@ -244,6 +253,7 @@ class InferenceEngineImpl {
   ti_engine_config cfg{};
   int capacity = 1;      // streams one device call holds
   int kv_bits = 16;      // 8: e4m3 KV cache (TI_BITS_KV8 at ti_engine_create; cfg.bits stays the weight format)
+  int lookahead = 0;     // > 0: a greedy request that runs alone verifies this many n-gram drafts per step
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -367,6 +377,7 @@ class InferenceEngineImpl {
     const int bits = engine_option(md, "turboinfer.weight_bits", "TI_WEIGHT_BITS", 0);
     cfg.bits = bits == 8 || bits == 16 ? bits : 4;
     kv_bits = kv_bits_option(md);
+    lookahead = lookahead_option(md, kv_bits);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = 0;
     cfg.device = gpu;
@@ -440,6 +451,7 @@ class InferenceEngineImpl {
     cfg.eps = 1e-5f;
     cfg.bits = compat ? 16 : bits;
     kv_bits = kv_bits_option(md);
+    lookahead = compat ? 0 : lookahead_option(md, kv_bits);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = compat ? 1 : 0;
     cfg.device = gpu;
@@ -652,9 +664,18 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
       }
       // the longest prompt sets the step count (steps = longest + new - 1 <= max_seq)
       const size_t steps_new = std::min(want, (size_t)im.cfg.max_seq + 1 - stride);
-      check(ti_engine_generate(im.eng, n, prompts.data(), lens.data(), (int)stride, nullptr, (int)steps_new, out.data(),
-                               nullptr),
-            "ti_engine_generate");
+      // a request that runs alone, with the lookahead option: the same tokens, several per step where the text
+      // repeats itself (no corpus, 3-grams); it needs k KV rows of head-room, without them the plain loop runs
+      if (im.lookahead > 0 && n == 1 && steps_new >= 1 &&
+          stride + steps_new - 1 + (size_t)im.lookahead <= (size_t)im.cfg.max_seq) {
+        check(ti_engine_generate_lookahead(im.eng, 0, prompts.data(), lens[0], 0, nullptr, 0, im.lookahead, 3,
+                                           (int)steps_new, out.data(), nullptr),
+              "ti_engine_generate_lookahead");
+      } else {
+        check(ti_engine_generate(im.eng, n, prompts.data(), lens.data(), (int)stride, nullptr, (int)steps_new,
+                                 out.data(), nullptr),
+              "ti_engine_generate");
+      }
       for (int m = 0; m < n; ++m) {
         const size_t b = budget(batches[c0 + m].size());
         for (size_t t = 0; t < std::min(b, steps_new); ++t) fresh[m].push_back(out[(size_t)m * steps_new + t]);

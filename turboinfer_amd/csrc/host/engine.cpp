@@ -133,6 +133,15 @@ struct ti_engine {
   int32_t* sc_targets = nullptr; // [max_seq]
   float* sc_lp = nullptr;        // [max_seq]
   int32_t* sc_top1 = nullptr;    // [max_seq]
+  // ti_engine_generate_lookahead (allocated by its first call, outside ti_engine_memory; the verify graphs,
+  // keyed (-(32 stream + R), splits) in `graphs`, bake these pointers: growing hist / out drops them)
+  float* la_logits = nullptr;    // [TI_LA_MAX_K + 1][vocab] logits of the verify rows
+  int32_t* la_state = nullptr;   // [TI_LA_STATE_WORDS] then cfg [4] (ti_lookahead_args)
+  int32_t* la_row_tok = nullptr; // [TI_LA_MAX_K + 1]
+  int32_t* la_hist = nullptr;    // [la_hist_cap] corpus ++ prompt ++ generated
+  int32_t* la_out = nullptr;     // [la_out_cap]
+  int la_hist_cap = 0, la_out_cap = 0;
+  float* la_ws = nullptr;        // ti_attn_prefill_split workspace (16 rows, 32 splits)
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -630,6 +639,8 @@ PfAttn prefill_attn_route(const ti_engine* e, int rows) {
   return prefill_attn_on() ? PF_ATTN_MFMA : PF_ATTN_DECODE;
 }
 
+int enqueue_prefill_layers(ti_engine* e, int m, int rows, int split_attn);
+
 int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
   const ti_engine_config& c = e->c;
   ++e->n_prefill_chunks;
@@ -653,6 +664,14 @@ int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
   sa.base_pos = e->pf_base;
   sa.step_ctr = e->pf_zero;
   TI_TRY(ti_step_begin(&sa, e->s));
+  return enqueue_prefill_layers(e, m, rows, 0);
+}
+
+// Every layer of a prompt chunk: `rows` rows of e->h at the positions in e->pos, through stream slot m's KV
+// cache (graph-capturable: nothing here touches the host).  split_attn > 0 (the lookahead verify step, at most
+// 16 rows of an fp16 cache): the attention is ti_attn_prefill_split with that many splits.
+int enqueue_prefill_layers(ti_engine* e, int m, int rows, int split_attn) {
+  const ti_engine_config& c = e->c;
   const int H = c.hidden, qd = e->qd(), kvd = e->kvd(), I = c.inter;
   for (int l = 0; l < c.layers; ++l) {
     DevLayer& L = e->layer[l];
@@ -676,7 +695,10 @@ int enqueue_prefill(ti_engine* e, int m, int t0, int rows, int base) {
     const bool pk = route == PF_ATTN_DECODE_PACKED;
     // (an e4m3 cache: on either route every row reads its keys, its own included, from the quantised
     // cache, as a decode step would)
-    if (route == PF_ATTN_MFMA && e->kv8)
+    if (split_attn > 0)
+      TI_TRY(ti_attn_prefill_split(e->q, kc, vc, c.max_seq, e->pos, rows, c.heads, c.kv_heads, c.head_dim, split_attn,
+                                   e->la_ws, e->attn, e->s));
+    else if (route == PF_ATTN_MFMA && e->kv8)
       TI_TRY(ti_attn_prefill_f8(e->q, reinterpret_cast<const uint8_t*>(kc), reinterpret_cast<const uint8_t*>(vc), c.max_seq,
                                 e->pos, rows, c.heads, c.kv_heads, c.head_dim, e->attn, e->s));
     else if (route == PF_ATTN_MFMA)
@@ -1580,6 +1602,184 @@ int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int 
   }
   TI_TRY(ti_memcpy_d2h(out_logprob, e->sc_lp, (size_t)n * 4, e->s));   // (synchronises the stream)
   if (out_top1) TI_TRY(ti_memcpy_d2h(out_top1, e->sc_top1, (size_t)n * 4, e->s));
+  return TI_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------ lookahead greedy decoding
+namespace {
+
+// Splits of the verify step's attention (ti_attn_prefill_split).  A split's time is its share of the keys plus
+// a merge that grows with the split count, so the best count goes with the square root of the keys and hardly
+// with the rows: 8 measured fastest at 2048 keys (4 / 8 / 16 / 32: 18.3 / 14.5 / 16.3 / 25.7 us, 7B shape, 8 or
+// 16 rows) and 16 at 8192 (55 / 32 / 25 / 30 us at 8 rows of the Llama-3-8B shape, 55 / 33 / 30 / 39 at 16;
+// profiles/lookahead_ab.txt) -- sqrt(max_seq / 32), with at most one wave per SIMD over the (query blocks x
+// kv-heads) and at most 32.  ti_engine_config.attn_splits overrides it as it does the decode attention's.
+int la_splits(const ti_engine* e, int R) {
+  const ti_engine_config& c = e->c;
+  if (c.attn_splits > 0) return std::min(c.attn_splits, 32);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  const int G = c.heads / c.kv_heads, qpw = std::max(1, 16 / G), blocks = (R + qpw - 1) / qpw * c.kv_heads;
+  const int by_keys = (int)std::lround(std::sqrt((double)c.max_seq / 32.0));
+  return std::max(1, std::min(std::min(by_keys, std::max(1, 4 * cus / blocks)), 32));
+}
+
+ti_lookahead_args la_args(ti_engine* e, int k) {
+  const ti_engine_config& c = e->c;
+  ti_lookahead_args a{};
+  a.state = e->la_state;
+  a.cfg = e->la_state + TI_LA_STATE_WORDS;
+  a.hist = e->la_hist;
+  a.k = k;
+  a.hidden = c.hidden;
+  a.vocab = c.vocab;
+  a.max_pos = c.max_seq - 1;
+  a.emb = e->emb;
+  a.h = e->h;
+  a.row_tok = e->la_row_tok;
+  a.pos = e->pos;
+  a.argmax = e->argmax;
+  a.out_tokens = e->la_out;
+  return a;
+}
+
+// One verify step of stream slot `stream`: the draft lookup, k + 1 rows through every layer as a prompt chunk
+// (positions from the device, key-split attention), the lm_head's greedy keys, accept / commit.
+int enqueue_verify(ti_engine* e, int stream, int k, int splits) {
+  const ti_engine_config& c = e->c;
+  const int R = k + 1;
+  const ti_lookahead_args a = la_args(e, k);
+  TI_TRY(ti_lookahead_begin(&a, e->s));
+  TI_TRY(enqueue_prefill_layers(e, stream, R, splits));
+  ti_epilogue el{};
+  el.kind = TI_EPI_LOGITS_ARGMAX;
+  el.ldo = c.vocab;
+  el.out = e->la_logits;
+  el.argmax = e->argmax;
+  TI_TRY(gemm_rows(e, e->lm, R, e->h, TI_X_F32_RMSNORM, c.hidden, e->out_norm, el, 4, false));
+  return ti_lookahead_accept(&a, e->s);
+}
+
+int get_verify_graph(ti_engine* e, int stream, int k, int splits, hipGraphExec_t* out) {
+  const auto key = std::make_pair(-(32 * stream + k + 1), splits);
+  auto it = e->graphs.find(key);
+  if (it != e->graphs.end()) {
+    *out = it->second;
+    return TI_OK;
+  }
+  TI_TRY(ti_gemm_prepare());
+  E_CHECK(hipStreamBeginCapture(e->s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
+  const int rc = enqueue_verify(e, stream, k, splits);
+  hipGraph_t g = nullptr;
+  const hipError_t ec = hipStreamEndCapture(e->s, &g);
+  if (rc != TI_OK) {
+    if (g) hipGraphDestroy(g);
+    return rc;
+  }
+  E_CHECK(ec, "hipStreamEndCapture");
+  hipGraphExec_t ex = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+  hipGraphDestroy(g);
+  E_CHECK(ei, "hipGraphInstantiate");
+  e->graphs[key] = ex;
+  *out = ex;
+  return TI_OK;
+}
+
+void drop_graphs(ti_engine* e) {
+  for (auto& g : e->graphs) hipGraphExecDestroy(g.second);
+  e->graphs.clear();
+}
+
+}  // namespace
+
+extern "C" {
+
+int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                                 const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
+                                 int32_t* out_tokens, ti_lookahead_stats* stats) {
+  const char* fn = "ti_engine_generate_lookahead";
+  if (!e || !prompt || !out_tokens || (!corpus && corpus_len != 0)) return ti_set_error(TI_ERR_ARG, "%s: null", fn);
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
+  if (e->kv8) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: TI_BITS_KV8 engine (no e4m3 key-split prefill attention)", fn);
+  if (stream < 0 || stream >= c.max_batch) return ti_set_error(TI_ERR_ARG, "%s: stream %d of %d", fn, stream, c.max_batch);
+  if (prompt_len < 1 || max_new < 1 || corpus_len < 0)
+    return ti_set_error(TI_ERR_ARG, "%s: prompt_len %d max_new %d corpus_len %d", fn, prompt_len, max_new, corpus_len);
+  if (k < 1 || k > TI_LA_MAX_K) return ti_set_error(TI_ERR_ARG, "%s: k %d outside [1, %d]", fn, k, TI_LA_MAX_K);
+  if (ngram < 1 || ngram > TI_LA_MAX_NGRAM)
+    return ti_set_error(TI_ERR_ARG, "%s: ngram %d outside [1, %d]", fn, ngram, TI_LA_MAX_NGRAM);
+  for (int i = 0; i < prompt_len; ++i)
+    if (prompt[i] < 0 || prompt[i] >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "%s: prompt token %d at %d outside [0, vocab %d)", fn, prompt[i], i, c.vocab);
+  for (int i = 0; i < corpus_len; ++i)
+    if (corpus[i] < 0 || corpus[i] >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "%s: corpus token %d at %d outside [0, vocab %d)", fn, corpus[i], i, c.vocab);
+  // the verify rows reach k slots past the last token fed
+  if (start_pos < 0 || (int64_t)start_pos + prompt_len + max_new - 1 + k > c.max_seq)
+    return ti_set_error(TI_ERR_ARG, "%s: start_pos %d + %d prompt + %d new - 1 + k %d > max_seq %d", fn, start_pos,
+                        prompt_len, max_new, k, c.max_seq);
+  const int64_t cap64 = (int64_t)corpus_len + prompt_len + max_new;
+  if (cap64 > (1 << 28)) return ti_set_error(TI_ERR_ARG, "%s: history of %lld tokens", fn, (long long)cap64);
+  const int cap = (int)cap64, R = k + 1;
+
+  if (!e->la_logits) {
+    TI_TRY(e->alloc_t(&e->la_logits, (size_t)(TI_LA_MAX_K + 1) * c.vocab));
+    TI_TRY(e->alloc_t(&e->la_state, (size_t)TI_LA_STATE_WORDS + 4));
+    TI_TRY(e->alloc_t(&e->la_row_tok, (size_t)TI_LA_MAX_K + 1));
+    void* w = nullptr;   // (alloc zeroes it: the tickets' one-time arming)
+    TI_TRY(e->alloc(&w, ti_attn_prefill_split_workspace_bytes(TI_LA_MAX_K + 1, c.heads, c.head_dim, 32)));
+    e->la_ws = static_cast<float*>(w);
+  }
+  if (cap > e->la_hist_cap || max_new > e->la_out_cap) {   // the verify graphs bake these buffers in
+    drop_graphs(e);
+    if (cap > e->la_hist_cap) {
+      TI_TRY(e->alloc_t(&e->la_hist, (size_t)cap));
+      e->la_hist_cap = cap;
+    }
+    if (max_new > e->la_out_cap) {
+      TI_TRY(e->alloc_t(&e->la_out, (size_t)max_new));
+      e->la_out_cap = max_new;
+    }
+  }
+  TI_TRY(ensure_io(e, prompt_len, 1));
+  TI_TRY(ti_memcpy_h2d(e->in_tokens + (size_t)stream * e->in_cap, prompt, (size_t)prompt_len * 4, e->s));
+  std::vector<int32_t> hist((size_t)corpus_len + prompt_len);
+  if (corpus_len) std::memcpy(hist.data(), corpus, (size_t)corpus_len * 4);
+  std::memcpy(hist.data() + corpus_len, prompt, (size_t)prompt_len * 4);
+  TI_TRY(ti_memcpy_h2d(e->la_hist, hist.data(), hist.size() * 4, e->s));
+  int32_t st[TI_LA_STATE_WORDS + 4] = {(int32_t)hist.size(), start_pos + prompt_len - 1, 0, 0, 0, 0, 0, 0,
+                                       ngram, max_new, e->stop_token, cap};
+  TI_TRY(ti_memcpy_h2d(e->la_state, st, sizeof(st), e->s));
+  // prompt[0 .. n - 2] as prompt chunks (ti_engine_score's chunk); prompt[n - 1] is row 0 of the first step
+  const int pf = e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16);
+  for (int t0 = 0; t0 < prompt_len - 1; t0 += pf)
+    TI_TRY(enqueue_prefill(e, stream, t0, std::min(pf, prompt_len - 1 - t0), start_pos));
+  hipGraphExec_t g = nullptr;
+  TI_TRY(get_verify_graph(e, stream, k, la_splits(e, R), &g));
+  // replays in growing chunks (4, 8, 16, .. 64), the state read back after each; at most max_new steps.  A
+  // replay after `done` changes nothing (begin writes padding rows, accept returns) but costs a whole step, a
+  // read-back costs microseconds: a chunk is no longer than the steps the rest needs at the tokens per step
+  // seen so far (17 steps of 7.5 tokens ran 28 replays without this, profiles/lookahead_ab.txt)
+  int ran = 0;
+  for (int chunk = 4; ran < max_new && !st[3]; chunk = std::min(chunk * 2, 64)) {
+    int S = std::min(chunk, max_new - ran);
+    if (st[4] > 0 && st[2] > 0)
+      S = std::min(S, std::max(1, (int)(((int64_t)(max_new - st[2]) * st[4] + st[2] - 1) / st[2])));
+    for (int i = 0; i < S; ++i) E_CHECK(hipGraphLaunch(g, e->s), "hipGraphLaunch");
+    ran += S;
+    TI_TRY(ti_memcpy_d2h(st, e->la_state, TI_LA_STATE_WORDS * 4, e->s));   // (synchronises the stream)
+  }
+  e->n_decode_steps += (uint64_t)st[4];
+  const int produced = std::min(std::max(st[2], 0), max_new);
+  if (produced) TI_TRY(ti_memcpy_d2h(out_tokens, e->la_out, (size_t)produced * 4, e->s));
+  for (int t = produced; t < max_new; ++t) out_tokens[t] = -1;
+  if (stats) *stats = ti_lookahead_stats{st[4], st[5], st[6], st[2]};
+  if (!st[3]) return ti_set_error(TI_ERR_HIP, "%s: not complete after %d verify steps (produced %d of %d)", fn, ran, st[2], max_new);
   return TI_OK;
 }
 

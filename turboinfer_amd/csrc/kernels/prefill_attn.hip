@@ -30,6 +30,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "common.hpp"
@@ -107,11 +108,28 @@ __device__ __forceinline__ void pf_split(float x, _Float16& hi, _Float16& lo) {
 // WPE: waves per SIMD the shallow-ring build must fit (2: at most 256 registers with the AGPRs)
 // KV8: the cache holds e4m3 bytes (ti_attn_prefill_f8); each K / V byte is widened exactly to the fp16
 // operand (e4m3x4_to_f16x4) right before its MFMA, everything after that is the fp16 instance's code
-template <int HD, int RING = TI_PF_RING, int WPE = 1, bool KV8 = false, typename KT = typename PfRaw<HD, KV8>::T>
+//
+// SPK (ti_attn_prefill_split): the key blocks of a (query block, kv-head) are cut over gridDim.z waves.
+// Blocks [0, kmin / 16] -- every column of the wave has a key in each of them -- are dealt evenly, split s
+// taking [s n / S, (s + 1) n / S), and the last split also takes the tail up to kmax / 16: a split that
+// has blocks gives every column a finite maximum in its first step, and the last split is never empty.
+// Keys of a pass that lie past the split's last block are masked like keys past the column's position.
+// Each split stores its unnormalised accumulators and (m, l) per column write-through into the workspace,
+// drains the stores and takes a ticket; the last arriver merges the S partials in split order (the result
+// does not depend on the arrival order), stores fp16 and re-arms the ticket (as gemv.hip splitk_merge).
+// Workspace: pf_split_tickets(heads) int32 tickets, then per (query block, kv-head, split) kPfPart<HD>
+// floats: the lane-major accumulators ((t * 64 + lane) * 4 + i), then m [16] and l [16] per column.
+template <int HD>
+constexpr int kPfPart = 16 * HD + 32;
+__host__ __device__ constexpr int pf_split_tickets(int heads) { return (heads + 63) / 64 * 64; }
+
+template <int HD, int RING = TI_PF_RING, int WPE = 1, bool KV8 = false, bool SPK = false,
+          typename KT = typename PfRaw<HD, KV8>::T>
 __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __restrict__ q, const KT* __restrict__ kc,
                                                           const KT* __restrict__ vc, int max_seq,
                                                           const int32_t* __restrict__ pos, int M, int heads, int gsh,
-                                                          float scale, uint16_t* __restrict__ out) {
+                                                          float scale, uint16_t* __restrict__ out,
+                                                          float* __restrict__ ws) {
   constexpr int DV = HD / 16, KW = HD / 32;   // K: one 32-dim MFMA step per u32x4
   constexpr int KN = KV8 ? KW / 2 : KW;       // u32x4 per lane and K row (e4m3: two steps per u32x4)
   using KRaw = typename PfRaw<HD, KV8>::K;
@@ -198,13 +216,23 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
   for (int t = 0; t < DV; ++t) acc[t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
   float m_run = -INFINITY, l_run = 0.0f;
   const int nkb = kmax / 16 + 1;
+  // this wave's blocks [b0, b1), the last key a column may count (pe) and the shortest column's (kmin_e);
+  // SPK: the split's share of the prefix (above), else all of it
+  int b0 = 0, b1 = nkb, pe = p, kmin_e = kmin;
+  if constexpr (SPK) {
+    const int S = gridDim.z, sp = blockIdx.z, nmin = kmin / 16 + 1;
+    b0 = __builtin_amdgcn_readfirstlane((int)((long)sp * nmin / S));
+    b1 = __builtin_amdgcn_readfirstlane(sp == S - 1 ? nkb : (int)((long)(sp + 1) * nmin / S));
+    pe = min(p, b1 * 16 - 1);
+    kmin_e = min(kmin, b1 * 16 - 1);
+  }
   // K / V blocks in flight: a ring of kPfRing blocks, each slot refilled right after its block
   // is consumed (one or two waves per SIMD: the ring, not other waves, hides the load latency)
   constexpr int kPfRing = RING;
   KRaw kr[kPfRing];
   VRaw vr[kPfRing][4];
 #pragma unroll
-  for (int u = 0; u < kPfRing; ++u) load(u, kr[u], vr[u]);   // past nkb: clamped rows, zero V
+  for (int u = 0; u < kPfRing; ++u) load(b0 + u, kr[u], vr[u]);   // past nkb: clamped rows, zero V
   // let the first blocks land before the loop: with loads of the prologue still in flight at the
   // loop head the compiler merges their (different) issue order with the loop's own and waits for
   // every load at the top of each pass; with none, the loop's count alone sets the waits
@@ -216,7 +244,7 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
 #define TI_PF_NB 2   // blocks per softmax step (at most; a divisor of the ring)
 #endif
   constexpr int NB = kPfRing % TI_PF_NB == 0 ? TI_PF_NB : kPfRing % 2 == 0 ? 2 : 1;
-  for (int kb0 = 0; kb0 < nkb; kb0 += kPfRing) {
+  for (int kb0 = b0; kb0 < b1; kb0 += kPfRing) {
 #pragma unroll
     for (int u = 0; u < kPfRing; u += NB) {
       // no exit inside the pass: blocks past nkb hold only keys past every column's position, so
@@ -261,8 +289,8 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) pv[b][i] = s[b][i];
-      if ((kb + NB) * 16 - 1 > kmin) {   // wave-uniform
-        const int lim = p - kb * 16 - 4 * g;
+      if ((kb + NB) * 16 - 1 > kmin_e) {   // wave-uniform
+        const int lim = pe - kb * 16 - 4 * g;
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -299,7 +327,10 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          pv[b][i] = __expf(pv[b][i] - m_run);   // a masked key: exp2(-inf) = 0 exactly
+          // a masked key: exp2(-inf) = 0 exactly.  (SPK: the cut of the ranges gives every column a key in a
+          // split's first block; a column without one would keep m -inf and must count nothing)
+          if constexpr (SPK) pv[b][i] = m_run == -INFINITY ? 0.0f : __expf(pv[b][i] - m_run);
+          else pv[b][i] = __expf(pv[b][i] - m_run);
           ps += pv[b][i];
         }
       l_run += ps;
@@ -347,9 +378,70 @@ __global__ __launch_bounds__(64, WPE) void attn_prefill_kernel(const float* __re
   }
   float lt = l_run + __shfl_xor(l_run, 16, 64);
   lt += __shfl_xor(lt, 32, 64);
+  if constexpr (SPK) {
+    const int S = gridDim.z;
+    if (S > 1) {   // publish this split's partial; the last arriver of the (query block, kv-head) merges
+      const int blk = qb * gridDim.y + kvh, me = blockIdx.z;
+      int32_t* ticket = (int32_t*)ws + blk;
+      constexpr int PART = kPfPart<HD>;
+      const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(ws + pf_split_tickets(heads) + (size_t)blk * S * PART);
+      auto poff = [&](int sp, int t) { return (uint32_t)((sp * PART + (t * 64 + lane) * 4) * 4); };
+      auto moff = [&](int sp, int w) { return (uint32_t)((sp * PART + 16 * HD + 16 * w + r) * 4); };   // w: 0 m, 1 l
+#pragma unroll
+      for (int t = 0; t < DV; ++t) __builtin_amdgcn_raw_buffer_store_b128(acc[t], rs, poff(me, t), 0, kAuxSc1Load);
+      if (g == 0) {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m_run), rs, moff(me, 0), 0, kAuxSc1Load);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lt), rs, moff(me, 1), 0, kAuxSc1Load);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      int arrived = 0;
+      if (lane == 0) arrived = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      arrived = __builtin_amdgcn_readfirstlane(arrived);
+      if (arrived != S - 1) return;
+      // the column's maximum over the splits: lane group g reads splits g, g + 4, .. (S <= 32)
+      float mx = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        mx = fmaxf(mx, __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, moff(min(g + 4 * j, S - 1), 0), 0, kAuxSc1Load)));
+      mx = xor32_max(xor16_max(mx));   // finite: the last split is never empty
+      // O and l in split order 0 .. S - 1, CH splits per round trip; an empty split (m -inf) weighs 0
+      constexpr int CH = 4;
+      f32x4 num[DV];
+#pragma unroll
+      for (int t = 0; t < DV; ++t) num[t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+      float den = 0.0f;
+      for (int s0 = 0; s0 < S; s0 += CH) {
+        f32x4 ld[CH][DV];
+        float lm[CH], ll[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int sp = min(s0 + c, S - 1);
+#pragma unroll
+          for (int t = 0; t < DV; ++t)
+            ld[c][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, poff(sp, t), 0, kAuxSc1Load));
+          lm[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, moff(sp, 0), 0, kAuxSc1Load));
+          ll[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, moff(sp, 1), 0, kAuxSc1Load));
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          if (s0 + c >= S) break;
+          const float f = lm[c] == -INFINITY ? 0.0f : __expf(lm[c] - mx);
+          den = fmaf(f, ll[c], den);
+#pragma unroll
+          for (int t = 0; t < DV; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) num[t][i] = fmaf(f, ld[c][t][i], num[t][i]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < DV; ++t) acc[t] = num[t];
+      lt = den;
+      if (lane == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
+    }
+  }
   // lane (r, g) holds O^T[dim DV (4g + i) + t][column r] in acc[t][i]: dims 4g DV .. 4g DV + 4 DV - 1
   // of column r's (row, head), contiguous
-  const float inv = 1.0f / lt;
+  const float inv = SPK ? (lt > 0.0f ? 1.0f / lt : 0.0f) : 1.0f / lt;
   const int row = q0 + (r >> gsh), hh = kvh * G + (r & (G - 1));
   if (row < M) {
     uint16_t* dst = out + ((size_t)row * heads + hh) * HD + 4 * g * DV;
@@ -770,17 +862,17 @@ static int pf_launch(const char* name, const float* q, const KT* k_cache, const 
   } else if (head_dim == 128) {
     if (deep)
       hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING_DEEP, 1, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache,
-                         max_seq, pos, M, heads, gsh, scale, out);
+                         max_seq, pos, M, heads, gsh, scale, out, (float*)nullptr);
     else
       hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING, 2, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
-                         pos, M, heads, gsh, scale, out);
+                         pos, M, heads, gsh, scale, out, (float*)nullptr);
   } else {
     if (deep)
       hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING_DEEP, 1, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache,
-                         max_seq, pos, M, heads, gsh, scale, out);
+                         max_seq, pos, M, heads, gsh, scale, out, (float*)nullptr);
     else
       hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING, 2, KV8>), grid, dim3(64), 0, s, q, k_cache, v_cache, max_seq,
-                         pos, M, heads, gsh, scale, out);
+                         pos, M, heads, gsh, scale, out, (float*)nullptr);
   }
   TI_LAUNCH_CHECK("attn_prefill_kernel");
   return TI_OK;
@@ -790,6 +882,48 @@ extern "C" int ti_attn_prefill(const float* q, const uint16_t* k_cache, const ui
                                const int32_t* pos, int M, int heads, int kv_heads, int head_dim, uint16_t* out,
                                ti_stream_t stream) {
   return pf_launch<false>("ti_attn_prefill", q, k_cache, v_cache, max_seq, pos, M, heads, kv_heads, head_dim, out, stream);
+}
+
+// ---------------------------------------------------------------- key-split form (a short chunk, a long prefix)
+// (query blocks) x kv_heads of a chunk of M <= 16 rows, at most `heads` (the tickets' count): the largest over
+// the group sizes G = heads / kv_heads the kernel takes
+static size_t pf_split_blocks(int M, int heads) {
+  size_t nb = 0;
+  for (int G = 1; G <= 16; G <<= 1)
+    if (heads % G == 0) nb = std::max(nb, (size_t)((M * G + 15) / 16) * (size_t)(heads / G));
+  return nb;
+}
+
+extern "C" size_t ti_attn_prefill_split_workspace_bytes(int M, int heads, int head_dim, int splits) {
+  if (M < 1 || M > 16 || heads < 1 || heads > 65535 || (head_dim != 64 && head_dim != 128) || splits < 1 || splits > 32) return 0;
+  return ((size_t)ti::pf_split_tickets(heads) + pf_split_blocks(M, heads) * (size_t)splits * (size_t)(16 * head_dim + 32)) * 4;
+}
+
+extern "C" int ti_attn_prefill_split(const float* q, const uint16_t* k_cache, const uint16_t* v_cache, int max_seq,
+                                     const int32_t* pos, int M, int heads, int kv_heads, int head_dim, int splits,
+                                     float* workspace, uint16_t* out, ti_stream_t stream) {
+  const char* name = "ti_attn_prefill_split";
+  if (!q || !k_cache || !v_cache || !pos || !out || !workspace) return ti_set_error(TI_ERR_ARG, "%s: null pointer", name);
+  if (M < 1 || M > 16 || heads < 1 || kv_heads < 1 || heads % kv_heads || max_seq < 1 || heads > 65535)
+    return ti_set_error(TI_ERR_ARG, "%s: bad sizes M=%d (1..16) heads=%d kv_heads=%d max_seq=%d", name, M, heads, kv_heads, max_seq);
+  if (splits < 1 || splits > 32) return ti_set_error(TI_ERR_ARG, "%s: splits %d outside [1, 32]", name, splits);
+  if (head_dim != 64 && head_dim != 128)
+    return ti_set_error(TI_ERR_UNSUPPORTED, "%s: head_dim %d not in {64,128}", name, head_dim);
+  const int G = heads / kv_heads;
+  if (G & (G - 1) || G > 16) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: heads / kv_heads %d not a power of 2 <= 16", name, G);
+  // (the partials sit behind one 2 GiB buffer resource per (query block, kv-head): 32 splits are 260 KiB)
+  const int gsh = __builtin_ctz(G), qpw = 16 >> gsh;
+  const dim3 grid((M + qpw - 1) / qpw, kv_heads, splits);   // grid.x * grid.y <= heads tickets (M <= 16)
+  const float scale = 1.0f / sqrtf((float)head_dim);
+  hipStream_t s = (hipStream_t)stream;
+  if (head_dim == 128)
+    hipLaunchKernelGGL((ti::attn_prefill_kernel<128, TI_PF_RING_DEEP, 1, false, true>), grid, dim3(64), 0, s, q, k_cache,
+                       v_cache, max_seq, pos, M, heads, gsh, scale, out, workspace);
+  else
+    hipLaunchKernelGGL((ti::attn_prefill_kernel<64, TI_PF_RING_DEEP, 1, false, true>), grid, dim3(64), 0, s, q, k_cache,
+                       v_cache, max_seq, pos, M, heads, gsh, scale, out, workspace);
+  TI_LAUNCH_CHECK("attn_prefill_kernel (split)");
+  return TI_OK;
 }
 
 extern "C" int ti_attn_prefill_f8(const float* q, const uint8_t* k_cache, const uint8_t* v_cache, int max_seq,
