@@ -430,6 +430,11 @@ int ti_attn_prefill_set_kernel(int mode);
  * "gemv_wq_kernel<4,4>", "gemm_rows_kernel", "gemm_tile_kernel" (bench / profile labels). */
 int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len);
 
+/* Launches of this process so far that took a one-row instance of gemv_wq_kernel (one row, the step's
+ * epilogue kind fixed at compile time; TI_GEMV_EPI_GENERIC=1 turns them off).  Counted when a launch
+ * is enqueued (or captured).  For parity tests and A/Bs; not a reference interface. */
+uint64_t ti_gemm_onerow_epi_launches(void);
+
 /* Same-run HBM calibration (bench lines): best-of-`reps` read GB/s of a `bytes` buffer streamed
  * once by 2 workgroups per CU, and hipMemcpyAsync device-to-device GB/s (read + write bytes).
  * Not a reference interface: the reference's benchmark times wall clock only

@@ -110,6 +110,7 @@ EXPORTED = [
     "ti_engine_read_kv",
     "ti_attn_prefill_split", "ti_attn_prefill_split_workspace_bytes", "ti_lookahead_begin", "ti_lookahead_accept",
     "ti_engine_generate_lookahead",
+    "ti_gemm_onerow_epi_launches",
 ]
 
 _lib = None
@@ -241,6 +242,9 @@ def lib() -> C.CDLL:
             L.ti_lookahead_accept.argtypes = [C.POINTER(LookaheadArgs), vp]
             L.ti_engine_generate_lookahead.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp,
                                                        C.POINTER(LookaheadStats)]
+        if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
+            L.ti_gemm_onerow_epi_launches.argtypes = []
+            L.ti_gemm_onerow_epi_launches.restype = u64
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]

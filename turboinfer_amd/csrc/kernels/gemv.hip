@@ -47,8 +47,14 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifndef TI_GEMV_RING_DELAY
 #define TI_GEMV_RING_DELAY 0
 #endif
+#ifndef TI_GEMV_ONEROW_RMS_EARLY
+// One-row instances with a folded input (XM_F16F): the row's rms before the stream (1) or behind it, where
+// the generic tail computes it (0).  Before the stream measured inside the run-to-run spread (7B 834.0 against
+// 830.9 tok/s, TinyLlama 1853 against 1867: profiles/onerow_epi_ab.txt), so it stays where it was.
+#define TI_GEMV_ONEROW_RMS_EARLY 0
+#endif
 #ifndef TI_GEMV_EXP
-#define TI_GEMV_EXP 0   // product build; tools/probe_gemv.hip compiles diagnostic variants
+#define TI_GEMV_EXP 0  // product build; tools/probe_gemv.hip compiles diagnostic variants
 #endif
 #if TI_GEMV_EXP & 4   // diagnostic: per-workgroup phase timestamps (s_memrealtime, 100 MHz)
 __device__ unsigned long long g_gemv_ts[4096 * 8];
@@ -89,12 +95,14 @@ __host__ __device__ constexpr int align16(int b) { return (b + 15) & ~15; }
 struct GemmKnobs {
   bool splitk = true;       // TI_GEMM_SPLITK=0: no split-K for under-filled tile grids
   bool rows_split = true;   // TI_GEMM_ROWS_SPLIT=0: all rows in one batched-rows workgroup
+  bool epi_generic = false; // TI_GEMV_EPI_GENERIC=1: no one-row instances of gemv_wq_kernel
 };
 __host__ inline const GemmKnobs& gemm_knobs() {
   static const GemmKnobs k = [] {
     GemmKnobs v;
     if (const char* e = getenv("TI_GEMM_SPLITK")) v.splitk = atoi(e) != 0;
     if (const char* e = getenv("TI_GEMM_ROWS_SPLIT")) v.rows_split = atoi(e) != 0;
+    if (const char* e = getenv("TI_GEMV_EPI_GENERIC")) v.epi_generic = atoi(e) != 0;
     return v;
   }();
   return k;
@@ -340,7 +348,9 @@ __device__ __forceinline__ void lds_barrier() {
 // G32: group-32 weights (TI_BITS_G32, GGUF Q4_0 / Q8_0 blocks): within a tile, lane l holds for
 // MFMA step s4 the 8 k = 32 s4 + 8 (l >> 4) + e, so each v_mfma_f32_16x16x32 reduces exactly one
 // 32-weight block; its scale (and, int4, its offset correction) is applied per step.
-template <int BITS, int XM, bool G32 = false, bool AFF = false>
+// EPI >= 0: the one-row instance of one epilogue kind (M == 1, at most one output per thread: see the
+// one-row tail behind the stream and onerow_epi() in launch_gemv); -1: the generic body.
+template <int BITS, int XM, bool G32 = false, bool AFF = false, int EPI = -1>
 __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p_tiles, const uint16_t* p_scales,
                                                                    const void* p_x, const float* p_aux, int p_mgk,
                                                                    int p_N, int p_kx, int p_ldo, const float* p_pre,
@@ -443,12 +453,12 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p
   // the compiler wait at the join): a residual element of our tiles, this step's position
   // of row tid, or a dummy word of x.
   // (p_pre / kind / ldo are preloaded: epi.out for RESID, epi.pos for QKV, else x)
-  const int kind = (p_mgk >> 18) & 7, ldo = p_ldo;
+  const int kind = EPI >= 0 ? EPI : (p_mgk >> 18) & 7, ldo = p_ldo;
   const int n_res = kind == TI_EPI_RESID_F32 ? ntl * a.M * 16 : 0;
   const float* pre_p;
   {
     const int idx = tid < n_res ? tid : 0;
-    const int tl = kOneRow ? idx >> 4 : idx / (a.M * 16), rem = idx - tl * a.M * 16, m = rem >> 4, n = rem & 15;
+    const int tl = kOneRow || EPI >= 0 ? idx >> 4 : idx / (a.M * 16), rem = idx - tl * a.M * 16, m = rem >> 4, n = rem & 15;
     pre_p = kind == TI_EPI_RESID_F32 ? p_pre + (size_t)m * ldo + (t0 + tl) * 16 + n
             : kind == TI_EPI_QKV_ROPE_KV ? p_pre + (tid < a.M ? tid : 0) : p_pre;
   }
@@ -599,7 +609,7 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p
   } else if constexpr (XM != XM_NORM1 && XM != XM_ATTN) {
     stage_x_generic<XM>(a, xl, red, 0);
   }
-  if (a.epi.kind == TI_EPI_QKV_ROPE_KV && tid < a.M) ((int*)(es + a.M * a.epi.head_dim))[tid] = __builtin_bit_cast(int, pre);
+  if ((EPI >= 0 ? kind : a.epi.kind) == TI_EPI_QKV_ROPE_KV && tid < a.M) ((int*)(es + a.M * a.epi.head_dim))[tid] = __builtin_bit_cast(int, pre);
   if (tid < 16) best_l[tid] = 0ull;
   lds_barrier();
   STAMP_MARK(ph_staged);
@@ -646,10 +656,56 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p
 
   // RoPE (cos, sin) of each row's position: issued now, consumed after the stream.
   float cs_reg = 0.0f;
-  const int n_cs = a.epi.kind == TI_EPI_QKV_ROPE_KV ? a.M * a.epi.head_dim : 0;
+  const int n_cs = EPI < 0 && a.epi.kind == TI_EPI_QKV_ROPE_KV ? a.M * a.epi.head_dim : 0;
   if (n_cs > 0) {
     const int hd = a.epi.head_dim, idx = tid < n_cs ? tid : 0, m = idx / hd, j = idx - m * hd;
     cs_reg = a.epi.rope_cs[(size_t)((const int*)(es + a.M * hd))[m] * hd + j];
+  }
+
+  // One-row instances (EPI >= 0): everything the tail needs that does not depend on the stream is worked
+  // out here, where the waves wait for the ring anyway.  Thread tid owns output (tile tid >> 4,
+  // n = tid & 15) -- the generic M <= 4 epilogue's assignment of outputs to waves and lanes, which
+  // the fold's per-wave sums of h^2 depend on; the launcher guarantees ntl * 16 <= kGemvThreads.
+  const bool o_ok = tid < ntl * 16;
+  const int o_tl = o_ok ? tid >> 4 : 0, o_ng = (t0 + o_tl) * 16 + (lane & 15);
+  [[maybe_unused]] float o_rms = 1.0f;            // XM_F16F: the row's rms (same sum in every wave)
+  [[maybe_unused]] void* o_out = nullptr;         // this thread's output element
+  [[maybe_unused]] uint16_t* o_fx = nullptr;      // RESID with fold: its fold_x element
+  [[maybe_unused]] float2 o_cs = {1.0f, 0.0f};    // ROPE: (cos, sin) of the pair at the row's position
+  [[maybe_unused]] int o_rot = 0;                 // ROPE: 0 = no rotation (v rows), 1 = even dim, 2 = odd dim
+  [[maybe_unused]] uint32_t o_ci = 0;             // ROPE: element index into the K / V cache
+  if constexpr (EPI >= 0) {
+    if constexpr (XM == XM_F16F && TI_GEMV_ONEROW_RMS_EARLY) {
+      float t = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t += lane + 64 * j < n_ss ? ss4[j] : 0.0f;
+      t = group_sum<kWave>(t);
+      o_rms = sqrtf(t / (float)a.K + a.eps);
+    }
+    if constexpr (EPI == TI_EPI_RESID_F32) {
+      o_out = (void*)pre_p;                        // (p_pre is epi.out: the residual is updated in place)
+      if (fold) o_fx = a.epi.fold_x + o_ng;
+    } else if constexpr (EPI == TI_EPI_SILU_MUL_F16) {
+      o_out = (uint16_t*)a.epi.out + (t0 + o_tl) * 8 + (lane & 7);
+    } else if constexpr (EPI == TI_EPI_LOGITS_ARGMAX) {
+      o_out = (float*)a.epi.out + o_ng;
+    } else if constexpr (EPI == TI_EPI_QKV_ROPE_KV) {
+      const ti_epilogue& e = a.epi;
+      const int hd = e.head_dim, p = ((const int*)(es + hd))[0];   // (staged before the barrier above)
+      const bool is_q = o_ng < e.q_dim, qk = o_ng < e.q_dim + e.kv_dim;
+      const int c = o_ng - (is_q ? 0 : e.q_dim) - (qk ? 0 : e.kv_dim);
+      const int kvh = c / hd, d = c - kvh * hd;
+      if (qk) {
+        o_rot = 1 + (d & 1);
+        o_cs = *(const float2*)(e.rope_cs + (size_t)p * hd + (d & ~1));
+      }
+      if (is_q) {
+        o_out = (float*)e.out + o_ng;
+      } else {
+        o_out = qk ? e.k_cache : e.v_cache;
+        o_ci = (uint32_t)((kvh * e.max_seq + p) * hd + d);
+      }
+    }
   }
 
   GEMV_TS(2);
@@ -761,6 +817,96 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p
   GEMV_TS(3);
   GEMV_WTS();
   STAMP_MARK(ph_streamed);
+  if constexpr (EPI >= 0) {
+    // ---- 5'. the one-row tail: nothing but the barrier between a wave's last item and the reduction.
+    // The residual and the fold weight of output tid are this thread's own prefetched words (the generic
+    // tail passes them through es[tid]); the 8 partials are read as the m = 0 component alone, all
+    // reads issued together, and summed in the generic order; the kind's arithmetic is epilogue()'s.
+    if constexpr (XM == XM_F16F && !TI_GEMV_ONEROW_RMS_EARLY) {   // (A/B form: the rms where the generic tail has it)
+      float t = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t += lane + 64 * j < n_ss ? ss4[j] : 0.0f;
+      t = group_sum<kWave>(t);
+      o_rms = sqrtf(t / (float)a.K + a.eps);
+    }
+    lds_barrier();
+    STAMP_MARK(ph_reduce);
+    float ssacc = 0.0f;
+    if (wave * kWave < ntl * 16) {   // (wave-uniform) the waves that own outputs
+      const float* sp = (const float*)(slab + o_tl * kSlabStride + (lane & 15));
+      float pw[kGemvWaves];
+#pragma unroll
+      for (int w = 0; w < kGemvWaves; ++w) pw[w] = sp[w * kWave * 4];
+      float v = pw[0];
+#pragma unroll
+      for (int w = 1; w < kGemvWaves; ++w) v += pw[w];
+      if constexpr (XM == XM_F16F) v = v / o_rms;
+      if constexpr (EPI == TI_EPI_RESID_F32) {
+        if (o_ok) {
+          const float r = pre + v;
+          *(float*)o_out = r;
+          if (fold) {
+            *o_fx = f2h(r * fw_pre);
+            ssacc = fmaf(r, r, ssacc);
+          }
+        }
+      } else if constexpr (EPI == TI_EPI_SILU_MUL_F16) {
+        const float up = lane_xor<8>(v);   // lanes n < 8: the up row n + 8 of the same tile
+        const float s = v / (1.0f + expf(-v));
+        if (o_ok && (lane & 8) == 0) *(uint16_t*)o_out = f2h(up * s);
+      } else if constexpr (EPI == TI_EPI_QKV_ROPE_KV) {
+        const float partner = lane_xor<1>(v);
+        float r = v;
+        if (o_rot == 1) r = fmaf(-partner, o_cs.y, v * o_cs.x);
+        else if (o_rot == 2) r = fmaf(v, o_cs.x, partner * o_cs.y);
+        if (o_ok) {
+          if (o_ng < a.epi.q_dim) *(float*)o_out = r;
+          else if (a.epi.kv_fp8) ((uint8_t*)o_out)[o_ci] = f2e4m3(r);
+          else ((uint16_t*)o_out)[o_ci] = f2h(r);
+        }
+      } else if constexpr (EPI == TI_EPI_LOGITS_ARGMAX) {
+        // the workgroup's key: a maximum, so any order of merging gives the generic tail's bits; each
+        // wave that owns outputs merges its own into the slot (no LDS pass, no second barrier)
+        unsigned long long best = 0ull;
+        if (o_ok) {
+          *(float*)o_out = v;
+          best = ((unsigned long long)float_order_key(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)o_ng);
+        }
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+          const unsigned long long other = __shfl_xor(best, o, kWave);
+          best = other > best ? other : best;
+        }
+        if (lane == 0 && best) atomicMax(a.epi.argmax + (bid & (TI_ARGMAX_SLOTS - 1)), best);
+      }
+    }
+    STAMP_MARK(ph_epi);
+    if constexpr (EPI == TI_EPI_LOGITS_ARGMAX) {
+      if (a.epi.step_ctr && bid == 0 && tid == 0) *a.epi.step_ctr += a.epi.advance;
+    }
+    if constexpr (EPI == TI_EPI_RESID_F32) {   // the workgroup's sum of h^2: the generic tail's two forms
+      if (fold && ntl * 16 <= kWave) {
+        if (wave == 0) {
+          const float sw = group_sum<kWave>(ssacc);
+          if (lane == 0) a.epi.fold_ss[bid] = sw;
+        }
+      } else if (fold) {
+        float* red2 = (float*)best_l;
+        const float sw = group_sum<kWave>(ssacc);
+        if (lane == 0) red2[wave] = sw;
+        lds_barrier();
+        if (tid == 0) {
+          float t = 0.0f;
+#pragma unroll
+          for (int w = 0; w < kGemvWaves; ++w) t += red2[w];
+          a.epi.fold_ss[bid] = t;
+        }
+      }
+    }
+    GEMV_TS(4);
+    stamp_end(a.stamp, t_entry, ph_issued, ph_staged, ph_stream, ph_streamed, ph_reduce, ph_epi, ph_streamed);
+    return;
+  }
   // ---- 5. epilogue inputs into LDS, reduce the 8 partials per tile, epilogue
   if (tid < n_res) es[tid] = pre;
   if (fold && tid < n_res) es[n_res + tid] = fw_pre;
@@ -2233,6 +2379,19 @@ __host__ inline int gemv_xmode(int x_kind, int M, int K) {
   return M == 1 && (K >> 3) <= kGemvThreads ? XM_NORM1 : XM_NORM;
 }
 
+// One-row instances of gemv_wq_kernel (EPI >= 0): one row, one of the step's (x mode,
+// epilogue kind) pairs (listed in launch_gemv), at most one output per thread, and a K / V cache whose
+// element index fits 32 bits.  TI_GEMV_EPI_GENERIC=1 routes every launch to the generic instance.
+static std::atomic<unsigned long long> g_onerow_epi_launches{0};
+__host__ inline bool onerow_epi(const GemvArgs& a, int xm, int grid) {
+  if (gemm_knobs().epi_generic || a.M != 1) return false;
+  if (xm != XM_F16F && xm != XM_ATTN && xm != XM_F16 && xm != XM_NORM1) return false;
+  const int NT = a.N >> 4;
+  if ((NT + grid - 1) / grid * 16 > kGemvThreads) return false;
+  if (a.epi.kind == TI_EPI_QKV_ROPE_KV && (long long)a.epi.kv_dim * a.epi.max_seq > 0x7fffffffll) return false;
+  return true;
+}
+
 template <int BITS, bool G32 = false, bool AFF = false>
 static int launch_gemv(const GemvArgs& a, int lds, hipStream_t s, int grid) {
   const float* pre = a.epi.kind == TI_EPI_RESID_F32 ? (const float*)a.epi.out
@@ -2247,6 +2406,28 @@ static int launch_gemv(const GemvArgs& a, int lds, hipStream_t s, int grid) {
   if (nt_q > 255 || nt_r >= (1 << 23))
     return ti_set_error(TI_ERR_UNSUPPORTED, "gemv_wq_kernel: %d tiles over %d workgroups", NT, grid);
   const int pn = nt_q | (nt_r << 8);
+  if constexpr (BITS != 16 && !G32 && !AFF) {
+    // one-row instances (gemv_wq_kernel EPI >= 0); anything else falls through to the generic ones
+#define TI_ONEROW(XMODE, KIND)                                                                                  \
+  if (xm == XMODE && a.epi.kind == KIND) {                                                                      \
+    hipLaunchKernelGGL((gemv_wq_kernel<BITS, XMODE, false, false, KIND>), dim3(grid), dim3(kGemvThreads), lds, s, \
+                       a.tiles, a.scales, a.x, aux, mgk, pn, kx, ldo, pre, a);                                  \
+    TI_LAUNCH_CHECK("gemv_wq_kernel");                                                                          \
+    g_onerow_epi_launches.fetch_add(1, std::memory_order_relaxed);                                              \
+    return TI_OK;                                                                                               \
+  }
+    if (onerow_epi(a, xm, grid)) {
+      TI_ONEROW(XM_F16F, TI_EPI_SILU_MUL_F16)
+      TI_ONEROW(XM_F16F, TI_EPI_LOGITS_ARGMAX)
+      TI_ONEROW(XM_F16F, TI_EPI_QKV_ROPE_KV)
+      TI_ONEROW(XM_ATTN, TI_EPI_RESID_F32)
+      TI_ONEROW(XM_F16, TI_EPI_RESID_F32)
+      TI_ONEROW(XM_NORM1, TI_EPI_SILU_MUL_F16)
+      TI_ONEROW(XM_NORM1, TI_EPI_LOGITS_ARGMAX)
+      TI_ONEROW(XM_NORM1, TI_EPI_QKV_ROPE_KV)
+    }
+#undef TI_ONEROW
+  }
   switch (xm) {
     case XM_F16: hipLaunchKernelGGL((gemv_wq_kernel<BITS, XM_F16, G32, AFF>), dim3(grid), dim3(kGemvThreads), lds, s, a.tiles, a.scales, a.x, aux, mgk, pn, kx, ldo, pre, a); break;
     case XM_F32: hipLaunchKernelGGL((gemv_wq_kernel<BITS, XM_F32, G32, AFF>), dim3(grid), dim3(kGemvThreads), lds, s, a.tiles, a.scales, a.x, aux, mgk, pn, kx, ldo, pre, a); break;
@@ -2478,8 +2659,19 @@ extern "C" int ti_gemm_prepare(void) {
       (const void*)gemv_wq_kernel<16, XM_NORM1>, (const void*)gemv_wq_kernel<16, XM_NORM>,
       (const void*)gemv_wq_kernel<4, XM_F16F>, (const void*)gemv_wq_kernel<8, XM_F16F>,
       (const void*)gemv_wq_kernel<16, XM_F16F>, (const void*)gemv_wq_kernel<4, XM_ATTN>,
-      (const void*)gemv_wq_kernel<8, XM_ATTN>, (const void*)gemv_wq_kernel<16, XM_ATTN>, TI_MB_FNS, TI_ROWS_FNS,
-      TI_TILE_FNS};
+      (const void*)gemv_wq_kernel<8, XM_ATTN>, (const void*)gemv_wq_kernel<16, XM_ATTN>,
+#define TI_ONEROW_FNS(B)                                                            \
+  (const void*)gemv_wq_kernel<B, XM_F16F, false, false, TI_EPI_SILU_MUL_F16>,       \
+  (const void*)gemv_wq_kernel<B, XM_F16F, false, false, TI_EPI_LOGITS_ARGMAX>,      \
+  (const void*)gemv_wq_kernel<B, XM_F16F, false, false, TI_EPI_QKV_ROPE_KV>,        \
+  (const void*)gemv_wq_kernel<B, XM_ATTN, false, false, TI_EPI_RESID_F32>,          \
+  (const void*)gemv_wq_kernel<B, XM_F16, false, false, TI_EPI_RESID_F32>,           \
+  (const void*)gemv_wq_kernel<B, XM_NORM1, false, false, TI_EPI_SILU_MUL_F16>,      \
+  (const void*)gemv_wq_kernel<B, XM_NORM1, false, false, TI_EPI_LOGITS_ARGMAX>,     \
+  (const void*)gemv_wq_kernel<B, XM_NORM1, false, false, TI_EPI_QKV_ROPE_KV>
+      TI_ONEROW_FNS(4), TI_ONEROW_FNS(8),
+#undef TI_ONEROW_FNS
+      TI_MB_FNS, TI_ROWS_FNS, TI_TILE_FNS};
   for (const void* f : fns)
     TI_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
                  "hipFuncSetAttribute(gemv_wq_kernel)");
@@ -2782,6 +2974,10 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
   if (name) snprintf(buf, (size_t)len, "%s", name);
   else snprintf(buf, (size_t)len, "gemv_wq_kernel<%d,%d>", bits, gemv_xmode(x_kind, M, K));
   return TI_OK;
+}
+
+extern "C" uint64_t ti_gemm_onerow_epi_launches(void) {
+  return ti::g_onerow_epi_launches.load(std::memory_order_relaxed);
 }
 
 extern "C" int ti_gemm_grid(int M, int N, int K) {
