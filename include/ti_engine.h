@@ -258,7 +258,8 @@ int ti_engine_last_tokens(ti_engine* e, int n_streams, int32_t* tokens);
  *   [6] workgroups that ran on a CU another workgroup of the launch also ran on (a count)
  *   [7..12] diagnostic builds (TI_STAMP_PHASES): wave 0's phase marks, entry -> mark, workgroup mean
  *   [13]    diagnostic builds: per workgroup, first -> last wave's end of stream, workgroup mean
- * *n_launch receives the launches per step. */
+ * *n_launch receives the launches per step.  With env TI_STAMP_RAW=<file> the stamp words as read are
+ * also written to that file (per-workgroup questions: tools/stamp_split_ends.py). */
 #define TI_STAMP_FIELDS 14
 enum { TI_STAMP_KIND_OTHER = 0, TI_STAMP_KIND_GEMV = 1, TI_STAMP_KIND_ATTN = 2, TI_STAMP_KIND_BEGIN = 3,
        TI_STAMP_KIND_ROWS = 4, TI_STAMP_KIND_TILE = 5, TI_STAMP_KIND_RMSNORM = 6, TI_STAMP_KIND_MB = 7 };

@@ -378,6 +378,11 @@ size_t ti_qkv_attn_xchg_bytes(int heads, int splits);
 size_t ti_qkv_attn_error_offset(int heads, int splits);
 /* 1 when ti_qkv_attn_partials has a kernel for this shape (0: it would return TI_ERR_UNSUPPORTED / ARG). */
 int ti_qkv_attn_supported(int bits, int K, int heads, int kv_heads, int head_dim, int splits);
+/* 1 when a ti_qkv_attn_partials launch of these weight bits and head_dim takes, in this process, the order
+ * with the v tile deferred into the attention loop (head_dim 128; env TI_QA_VDEFER=0, read once per process,
+ * keeps the old order: k and v tiles, gather, attention).  Both orders write the same bytes.  For parity
+ * tests and A/Bs; not a reference interface. */
+int ti_qkv_attn_v_deferred(int bits, int head_dim);
 /* Prefill attention (forward_pass over a prompt chunk, inference_engine.cpp:1429-1491 ->
  * multi_head_attention, tensor_engine.cpp:1149-1252): the M rows are tokens of ONE stream whose
  * cache k_cache / v_cache [kv_heads][max_seq][head_dim] fp16 already holds their K / V; row m

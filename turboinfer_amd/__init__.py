@@ -111,6 +111,7 @@ EXPORTED = [
     "ti_attn_prefill_split", "ti_attn_prefill_split_workspace_bytes", "ti_lookahead_begin", "ti_lookahead_accept",
     "ti_engine_generate_lookahead",
     "ti_gemm_onerow_epi_launches",
+    "ti_qkv_attn_v_deferred",
 ]
 
 _lib = None
@@ -245,6 +246,8 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
+        if hasattr(L, "ti_qkv_attn_v_deferred"):   # (older TI_LIB builds in A/B runs lack it)
+            L.ti_qkv_attn_v_deferred.argtypes = [i32, i32]
         L.ti_engine_compat_step.argtypes = [vp, i32, vp]
         L.ti_engine_replay_prepare.argtypes = [vp, i32, i32, i32]
         L.ti_engine_replay_run.argtypes = [vp, i32]

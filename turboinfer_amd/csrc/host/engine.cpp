@@ -2169,6 +2169,19 @@ int ti_engine_stamp_steps(ti_engine* e, int steps, int cap, int32_t* info_out, d
   if (g) hipGraphExecDestroy(g);
   ti_free(buf);
   TI_TRY(rc);
+  // TI_STAMP_RAW=<file> (diagnostic): the stamp words as read, for per-workgroup questions the means below cannot
+  // answer -- uint64 {launches per step, steps, words per workgroup}, int32 info[3 n], uint64 offs[n steps], the words
+  if (const char* raw = getenv("TI_STAMP_RAW")) {
+    if (FILE* f = fopen(raw, "wb")) {
+      const unsigned long long hdr[3] = {n, (unsigned long long)steps, (unsigned long long)kStampWords};
+      std::vector<unsigned long long> o64(offs.begin(), offs.end());
+      fwrite(hdr, 8, 3, f);
+      fwrite(info.data(), 4, 3 * n, f);
+      fwrite(o64.data(), 8, nt, f);
+      fwrite(h.data(), 8, words, f);
+      fclose(f);
+    }
+  }
   // per launch (all steps): first / last entry, last end, median workgroup end, mean wave-end skew,
   // workgroups sharing a CU, phase marks
   constexpr double kUs = 0.01;   // s_memrealtime: 100 MHz

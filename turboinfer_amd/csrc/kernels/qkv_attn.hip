@@ -69,6 +69,9 @@ constexpr int kQaWaves = 8, kQaThreads = kQaWaves * kWave;
 // 1712; profiles/r6_qa_ab.txt)
 #define TI_QA_KV_LATE -1
 #endif
+#ifndef TI_QA_Q_NT
+#define TI_QA_Q_NT 0   // head_dim 128: the q part's weights with the non-temporal policy of the k / v tiles' (A/B)
+#endif
 constexpr int kQaSlot = 32;   // granules per workgroup: the q part's 16, then 8 per k / v tile (k_p / v_p pairs)
 constexpr int kQaMaxK = 4096;
 constexpr int kQaMaxKv = 2;      // k / v tiles per workgroup (MHA at 8 splits: a k and a v tile each)
@@ -95,8 +98,16 @@ __host__ __device__ inline int qa_kv_tile(int h, int s, int i, int heads, int sp
 // NQ: q items per wave (k-tiles of the part / 8), NK: items per wave of a k / v tile (k-tiles / 8): compile-time,
 // so the weight loads need no branch (a branch around a load whose value feeds a phi makes the compiler
 // wait for it at once)
-template <int BITS, int HD, int NQ, int NK>
+//
+// VD (head_dim 128 only, DESIGN 4.19 "the v tile deferred"): the attention starts before the v tile.  The v
+// tile's weights are requested behind the staging barrier (younger than the RoPE pair, older than everything
+// after the q part).  After the q part: publish, the k tile's items, the q granules' loads, the K/V ring behind
+// them (a counted wait returns the granules with the ring in flight), the gather; the k epilogue by wave 2
+// behind the gather barrier; the v tile's items two per consumed slot in the first ring round, then one barrier
+// and the v epilogue by wave 3.  Same items, same fmaf chains, same reduction order: the same bytes.
+template <int BITS, int HD, int NQ, int NK, bool VD = false>
 __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnArgs a) {
+  static_assert(!VD || (HD == 128 && NK % NQ == 0), "the deferred v tile: head_dim 128 (a k and a v tile per workgroup)");
   const unsigned long long t_entry = stamp_now();
   constexpr int C = TileFmt<BITS>::kChunks;
   constexpr int QT = HD / 16;                 // q tiles of a head
@@ -161,7 +172,10 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
   for (int i = 0; i < NQ; ++i) {
     const u32x4* src = a.tiles + ((size_t)gq * KT + kp * KTP + wave + kQaWaves * i) * (kWave * C) + lane;
 #pragma unroll
-    for (int c = 0; c < C; ++c) wq[i][c] = *(src + c * kWave);
+    for (int c = 0; c < C; ++c) {
+      if constexpr (HD == 128 && TI_QA_Q_NT) wq[i][c] = __builtin_nontemporal_load(src + c * kWave);
+      else wq[i][c] = *(src + c * kWave);
+    }
   }
   // The k / v tiles' weights: at head_dim 128 (MHA: every workgroup exactly kQaMaxKv tiles, checked on the
   // host) right behind the q part's, with no branch, so the CU's queue stays full from the start; with a
@@ -180,7 +194,18 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
           for (int c = 0; c < C; ++c) wk[t][i][c] = __builtin_nontemporal_load(src + c * kWave);
         }
   };
-  if constexpr (kKvwUniform && !TI_QA_KVW_LATE) load_kv_weights();
+  // (the deferred order: the k tile's weights here, the v tile's behind the staging barrier -- its items run in the
+  // attention loop, and loads older than the q gather's granules are waited for with them: vmcnt is in order)
+  auto load_kv_tile = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      const u32x4* src = a.tiles + ((size_t)(t ? gk[1] : gk[0]) * KT + wave + kQaWaves * i) * (kWave * C) + lane;
+#pragma unroll
+      for (int c = 0; c < C; ++c) wk[t][i][c] = __builtin_nontemporal_load(src + c * kWave);
+    }
+  };
+  if constexpr (VD) load_kv_tile(0);
+  else if constexpr (kKvwUniform && !TI_QA_KVW_LATE) load_kv_weights();
   // every weight load issued before the staging's first wait: memory ops cannot cross the first asm, and
   // the small loads' values pass through the second, so no use of them is scheduled above the loads
   asm volatile("" ::: "memory");
@@ -232,6 +257,11 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
   }
 
   if constexpr (!kKvwUniform && !TI_QA_KVW_LATE) load_kv_weights();
+  if constexpr (VD) {
+    asm volatile("" ::: "memory");   // (the RoPE pair stays older than the v tile's weights: it is waited for first)
+    load_kv_tile(1);
+    asm volatile("" ::: "memory");
+  }
 
 
   // ---- 3. the K/V ring of the attention goes out now (its addresses need only p)
@@ -291,8 +321,108 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
   asm volatile("" ::: "memory");
   STAMP_MARK(ph_qpart);
 #if TI_QA_KVW_LATE   // the k / v tiles' weights only now: nothing competes with the q part's bytes
-  load_kv_weights();
+  if constexpr (!VD) load_kv_weights();
 #endif
+  // the k / v tiles' epilogue, tile ik of the workgroup, by one wave: the slab rows summed in wave order, / rms,
+  // RoPE of k, the cache row and the per-q-head copies
+  auto kv_epilogue = [&](int ik, bool is_k) {   // (is_k: a constant at each call)
+    const int n = lane & 15;
+    float v = slab[1 + ik][0][n];
+#pragma unroll
+    for (int w = 1; w < kQaWaves; ++w) v += slab[1 + ik][w][n];
+    v = v / rms;
+    const float partner = lane_xor<1>(v);
+    if (lane < 16) {
+      const int ng = (ik ? gk[1] : gk[0]) * 16 + n;
+      float rr = v;
+      if (is_k) {
+        const int d = (ng - qd) % HD;
+        rr = (d & 1) == 0 ? fmaf(-partner, cs.y, v * cs.x) : fmaf(v, cs.x, partner * cs.y);
+      }
+      const int c = ng - qd - (is_k ? 0 : kvd), kvh = c / HD, dd = c - kvh * HD;
+      const uint16_t hv = f2h(rr);
+      (is_k ? a.kc : a.vc)[((size_t)kvh * a.max_seq + p) * HD + dd] = hv;
+      // the row's fp16 values in pairs {lo | hi << 16, generation} for the split that attends the new key
+      const uint32_t pair = (uint32_t)hv | (lane_xor_u32<1>((uint32_t)hv) << 16);
+      if ((n & 1) == 0) st_sc1_u64(my_slot + 16 + ik * 8 + (n >> 1), ((unsigned long long)gen << 32) | pair);
+    }
+  };
+  // wave 0: the q part's 16 sums over the 8 waves (fixed order), published
+  auto publish_q = [&]() {
+    if (wave == 0 && lane < 16 && (int)blockIdx.x != a.drop) {
+      float v = slab[0][0][lane];
+#pragma unroll
+      for (int w = 1; w < kQaWaves; ++w) v += slab[0][w][lane];
+      st_sc1_u64(my_slot + lane, ((unsigned long long)gen << 32) | __builtin_bit_cast(uint32_t, v));
+    }
+  };
+  // q dim d of the head from its parts' sum: / rms, RoPE (tensor_engine.cpp:1602-1612, the fused epilogue's pattern)
+  auto q_finish = [&](int d, float v) {
+    v = v / rms;
+    const float partner = lane_xor<1>(v);
+    q_s[d] = (d & 1) == 0 ? fmaf(-partner, cs.y, v * cs.x) : fmaf(v, cs.x, partner * cs.y);
+  };
+  unsigned long long ph_kv = 0, ph_kitems = 0, ph_first = 0, ph_vbar = 0;   // (phase marks, diagnostic builds)
+#define TI_QA_MARK(var) do { if (TI_STAMP_PHASES) var = stamp_now(); } while (0)
+  if constexpr (VD) {
+    // ---- 5'. the deferred order: publish, the k items, the q granules' loads, the K/V ring behind them, the
+    // gather by threads < HD
+    constexpr int KP = NK / NQ;              // k-parts of a q tile (= S / QT, checked on the host)
+    // (the RoPE pair waited for before any ring load is out -- with the q and k weights, which the k items need
+    // now, and without the v tile's, which are younger: a later first use, or re-use of its registers, waits
+    // for the whole ring where the waves' paths join)
+    asm volatile("" : "+v"(cs.x), "+v"(cs.y));
+    // the k tile's items: about the time the siblings' q parts take to become visible
+    auto k_items = [&]() {
+      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int i = 0; i < NK; ++i) item(wk[0][i], wave + kQaWaves * i, &sl[1][0][0], acc);
+      if (lane < 16) slab[1][wave][lane] = acc[0];
+    };
+    // Every wave runs the same loads in the same order (the other waves read a granule too and drop it): where
+    // paths with different loads in flight join, the compiler's counted waits fall back to the lowest count, and
+    // the first ring slot, or the v items, would wait for the whole ring.
+    publish_q();
+    k_items();
+    TI_QA_MARK(ph_kitems);
+    const int d = tid & (HD - 1), t = d >> 4, n = d & 15;
+    const unsigned long long* g[KP];
+    unsigned long long x[KP];
+#pragma unroll
+    for (int part = 0; part < KP; ++part) {
+      g[part] = a.xchg + ((size_t)h * S + t + QT * part) * kQaSlot + n;
+      x[part] = ld_sc1_u64(g[part]);
+    }
+    asm volatile("" ::: "memory");   // (the granule loads stay older than the ring: vmcnt is in order)
+#pragma unroll
+    for (int q = 0; q < RA; ++q) arefill(q);
+    // the tags' first use stands behind the ring's issue and waits for the granules alone (vmcnt(2 RA): the ring
+    // stays in flight); a re-poll is younger than the ring and waits for all of it -- taken only on a miss
+#pragma unroll
+    for (int part = 0; part < KP; ++part) asm volatile("" : "+v"(x[part])::"memory");
+    if (tid < HD) {
+      bool miss = false;
+#pragma unroll
+      for (int part = 0; part < KP; ++part) miss |= (unsigned)(x[part] >> 32) != gen;
+      if (__builtin_expect(miss, 0)) {
+        bool lost = false;
+#pragma unroll
+        for (int part = 0; part < KP; ++part) {
+          unsigned spin = 0;
+          while ((unsigned)(x[part] >> 32) != gen && ++spin < kQaSpin) {
+            __builtin_amdgcn_s_sleep(1);
+            x[part] = ld_sc1_u64(g[part]);
+          }
+          lost |= spin >= kQaSpin;
+        }
+        if (lost) st_sc1_u32(a.err + (tid & 1), 1u);   // (a per-lane address: one vector store)
+      }
+      float v = 0.0f;
+#pragma unroll
+      for (int part = 0; part < KP; ++part) v += __builtin_bit_cast(float, (uint32_t)x[part]);
+      q_finish(d, v);
+    }
+  } else {   // ---- the old order
   if constexpr (kKvLate) {   // the K/V ring after the q part: the keys then do not compete with the q stream
 #pragma unroll
     for (int q = 0; q < RA; ++q) arefill(q);
@@ -317,7 +447,7 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
     __builtin_amdgcn_s_barrier();   // (uniform: nkv is the workgroup's)
     asm volatile("" ::: "memory");
   }
-  STAMP_MARK(ph_kv);
+  TI_QA_MARK(ph_kv);
   // waves 2, 3: the k / v tiles' epilogues (/ rms, RoPE of k, the cache row and the per-q-head copies)
   if (wave >= 2 && wave - 2 < nkv) {
     const int ik = wave - 2, n = lane & 15;
@@ -366,10 +496,13 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
     const float rr = (d & 1) == 0 ? fmaf(-partner, cs.y, v * cs.x) : fmaf(v, cs.x, partner * cs.y);
     q_s[d] = rr;
   }
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   STAMP_MARK(ph_gathered);
+  if constexpr (VD)
+    if (wave == 2) kv_epilogue(0, true);   // the k tile's epilogue while the other waves start the attention
 
   // the new key (position p) of the head's kv-head: attended by the last wave of split S - 1 after its old keys
   constexpr int kNewWave = kQaWaves - 1;
@@ -420,6 +553,43 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
     consume_key(kv, vv, valid);
   };
   int a0 = 0;
+  f32x4 vacc = {0.0f, 0.0f, 0.0f, 0.0f};   // the deferred v tile's items: one fmaf chain in item order
+  auto v_item = [&](int i) { item(wk[1][i], wave + kQaWaves * i, &sl[2][0][0], vacc); };
+  // the deferred v tile: kVps items behind each of the first consumed slots, then the wave's slab row and ONE barrier
+  // that every wave passes exactly once, whatever its slot count -- in the first main round, or in front of the
+  // ring's tail for a wave with fewer than RA slots; behind it wave 3 publishes the v row.  The new-key wave of
+  // split S - 1 waits for the v rows of every split's workgroups (its own workgroup's among them at MHA: v tiles
+  // of kv-heads 0-3 belong to split S - 1), so the barrier stands before that wave's granule loads and as early
+  // as the items allow: behind the main rounds it made split S - 1 the launch's tail (profiles/qa_vdefer_ab.txt)
+  constexpr int kVps = 2, kVslots = (NK + kVps - 1) / kVps;
+  static_assert(!VD || kVslots <= RA, "the v items fit the first main round");
+  auto v_publish = [&]() {
+    if (lane < 16) slab[2][wave][lane] = vacc[0];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    TI_QA_MARK(ph_vbar);
+    if (wave == 3) kv_epilogue(1, false);
+  };
+  if constexpr (VD) {
+    if (RA <= atot) {
+#pragma unroll
+      for (int q = 0; q < RA; ++q) {
+        ring_pin(kr[q], vr[q], lrun);
+        consume(kr[q], vr[q]);
+        arefill(q);
+        if (q == 0) TI_QA_MARK(ph_first);
+#pragma unroll
+        for (int i = q * kVps; i < (q + 1) * kVps && i < NK; ++i) v_item(i);
+        if (q == kVslots - 1) v_publish();
+      }
+      a0 = RA;
+    } else {
+#pragma unroll
+      for (int i = 0; i < NK; ++i) v_item(i);
+      v_publish();
+    }
+  }
   for (; a0 + RA <= atot; a0 += RA) {
 #pragma unroll
     for (int q = 0; q < RA; ++q) {
@@ -500,7 +670,11 @@ __global__ __launch_bounds__(kQaThreads, 1) void qkv_attn_kernel(const QkvAttnAr
     if (d == 0) *(float2*)(a.part_ml + 2 * rrow) = make_float2(mx, l);
   }
   STAMP_MARK(ph_end);
-  stamp_end(a.stamp, t_entry, ph_staged, ph_qdata, ph_qpart, ph_kv, ph_gathered, ph_attn, ph_end);
+  // phase marks: staged, q items, q part barrier, k / v items, gathered, attention; the deferred order: staged, k
+  // items, gathered, wave 0's first slot consumed, the v barrier, attention (the q part's marks are the old order's)
+  if constexpr (VD) stamp_end(a.stamp, t_entry, ph_staged, ph_kitems, ph_gathered, ph_first, ph_vbar, ph_attn, ph_end);
+  else stamp_end(a.stamp, t_entry, ph_staged, ph_qdata, ph_qpart, ph_kv, ph_gathered, ph_attn, ph_end);
+#undef TI_QA_MARK
 }
 
 }  // namespace ti
@@ -523,6 +697,19 @@ extern "C" size_t ti_qkv_attn_error_offset(int heads, int splits) { return qa_gr
 static bool qa_has_kernel(int bits, int head_dim, int nq, int nk, bool kv_uniform) {
   if (head_dim == 64) return (bits == 4 || bits == 8) && ((nq == 1 && (nk == 1 || nk == 2)) || (nq == 2 && nk == 2));
   return head_dim == 128 && (bits == 4 || bits == 8) && nq == 4 && nk == 4 && kv_uniform;
+}
+
+// TI_QA_VDEFER=0: the head_dim-128 instances keep the old order (the k and v tiles, then the gather, then the
+// attention) instead of the deferred v tile; read once per process (thread-safe static init)
+static bool qa_vdefer_knob() {
+  static const bool on = [] {
+    const char* v = getenv("TI_QA_VDEFER");
+    return v ? atoi(v) != 0 : true;
+  }();
+  return on;
+}
+extern "C" int ti_qkv_attn_v_deferred(int bits, int head_dim) {
+  return head_dim == 128 && (bits == 4 || bits == 8) && qa_vdefer_knob() ? 1 : 0;
 }
 
 extern "C" int ti_qkv_attn_supported(int bits, int K, int heads, int kv_heads, int head_dim, int splits) {
@@ -613,21 +800,26 @@ extern "C" int ti_qkv_attn_partials(const void* tiles, const uint16_t* scales, i
                         kQaMaxKv);
   const int nq = KT / (splits / QT) / kQaWaves, nk = KT / kQaWaves, key = nq * 10 + nk;
   const dim3 g(grid), blk(kQaThreads);
-#define TI_QA_CASE(B, H, Q, KK)                                                          \
-  if (bits == B && head_dim == H && key == Q * 10 + KK) {                                \
-    hipLaunchKernelGGL((qkv_attn_kernel<B, H, Q, KK>), g, blk, 0, s, a);               \
+  const bool vd = ti_qkv_attn_v_deferred(bits, head_dim) != 0;
+#define TI_QA_CASE_VD(B, H, Q, KK, V)                                                    \
+  if (bits == B && head_dim == H && key == Q * 10 + KK && vd == V) {                     \
+    hipLaunchKernelGGL((qkv_attn_kernel<B, H, Q, KK, V>), g, blk, 0, s, a);            \
     TI_LAUNCH_CHECK("qkv_attn_kernel");                                                  \
     return TI_OK;                                                                        \
   }
+#define TI_QA_CASE(B, H, Q, KK) TI_QA_CASE_VD(B, H, Q, KK, false)
   TI_QA_CASE(8, 64, 1, 2)   // TinyLlama-1.1B (K 2048, 8 splits: two k-parts of 8 k-tiles)
   TI_QA_CASE(4, 64, 1, 2)
   TI_QA_CASE(8, 64, 1, 1)   // K 1024, 4 splits
   TI_QA_CASE(4, 64, 1, 1)
   TI_QA_CASE(8, 64, 2, 2)   // K 2048, 4 splits
   TI_QA_CASE(4, 64, 2, 2)
-  TI_QA_CASE(4, 128, 4, 4)  // Llama-2-7B (K 4096, 8 splits: one q tile each)
+  TI_QA_CASE_VD(4, 128, 4, 4, true)  // Llama-2-7B (K 4096, 8 splits: one q tile each), the v tile deferred
+  TI_QA_CASE_VD(8, 128, 4, 4, true)
+  TI_QA_CASE(4, 128, 4, 4)           // TI_QA_VDEFER=0: the old order
   TI_QA_CASE(8, 128, 4, 4)
 #undef TI_QA_CASE
+#undef TI_QA_CASE_VD
   return ti_set_error(TI_ERR_UNSUPPORTED, "ti_qkv_attn_partials: no kernel for bits %d, head_dim %d, %d q / %d k-v items per wave",
                       bits, head_dim, nq, nk);
 }
