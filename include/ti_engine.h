@@ -136,6 +136,18 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int prompt_len, i
  * [n_req] = tokens produced (the eos token included). */
 int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new, int eos_token,
                     int chunk, int32_t* out_tokens, int32_t* out_len);
+/* ti_engine_serve with the step graph's sampler on (ti_sample_step, as in ti_engine_generate_sampled):
+ * request r's t-th new token is sample_next_token(its logits, temperature, top_k, top_p, draws[r][t]),
+ * whatever slot and chunk it runs in.  Every chunk starts at step 0 with one token per slot, so before a chunk
+ * the host places each live slot's next draws into that slot's row of the engine's draw buffer, and after it
+ * reads the slot's log-probabilities back.  Draws of a request cut short by eos_token are unused.
+ * draws (host, [n_req][max_new]); out_logprobs (host, [n_req][max_new], nullable): log p of each token, 0.0
+ * past out_len.  1 <= top_k <= vocab; top_k = 1 returns ti_engine_serve's tokens.  The sampler's parameters
+ * and buffers are baked into the step graphs: a change drops them (ti_engine_generate_sampled).
+ * TI_ERR_ARG before anything is enqueued: ti_engine_serve's, null draws, top_k outside [1, vocab]. */
+int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new,
+                            int eos_token, int chunk, float temperature, int top_k, float top_p, const float* draws,
+                            int32_t* out_tokens, int32_t* out_len, float* out_logprobs);
 
 /* Teacher-forced scoring of a token sequence on the device (InferenceEngine::compute_logprobs,
  * inference_engine.cpp:873-954; Quantizer::validate_quantization_accuracy is built on it,
@@ -189,6 +201,29 @@ typedef struct ti_lookahead_stats { int32_t steps, drafted, accepted, produced; 
 int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
                                  const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
                                  int32_t* out_tokens, ti_lookahead_stats* stats);
+
+/* Lookahead decoding of ONE SAMPLED request: new token number t (0-based) is sample_next_token(logits after
+ * the text so far, temperature, top_k, top_p, draws[t]) -- what ti_engine_generate_sampled computes for one
+ * stream with the same draws -- several tokens per verify step.  The step is ti_engine_generate_lookahead's
+ * with ti_lookahead_sample (ti_hip.h) between the lm_head and ti_lookahead_accept: row j is sampled with
+ * draws[produced + j], and draft j + 1 is kept iff it equals row j's sampled token.  This is not rejection
+ * sampling: the output is the sequential sampler's sequence for these draws, up to rounding between kernel
+ * routes (the verify rows run the batched-rows kernels, a decode step the one-row ones).  top_k = 1 is the
+ * greedy call with log-probabilities.
+ * Everything ti_engine_generate_lookahead documents applies: the prompt chunks, the chunked replay with the
+ * state read-back, ti_engine_set_stop, the counters, the k rows of head-room, what the slot's KV holds on return
+ * and how generation continues.  draws (host, [max_new]).  out_logprobs (host, [max_new], nullable): log p of
+ * each sampled token, 0.0 where out_tokens is -1.
+ * The sampled verify graph is cached next to the greedy one (its own key); both stay valid side by side.  The
+ * sampler's parameters, its workspace (top_k > TI_SAMPLE_MAX_K: TI_LA_MAX_K + 1 rows) and the device draw /
+ * log-probability buffers are baked into it: when one of them changes or grows, every cached graph is dropped
+ * and recaptured on demand, as ti_engine_generate_sampled does.
+ * TI_ERR_ARG before anything is enqueued: those of ti_engine_generate_lookahead, null draws, top_k outside
+ * [1, vocab].  TI_ERR_UNSUPPORTED: a compat engine, a TI_BITS_KV8 engine. */
+int ti_engine_generate_lookahead_sampled(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                                         const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
+                                         float temperature, int top_k, float top_p, const float* draws,
+                                         int32_t* out_tokens, float* out_logprobs, ti_lookahead_stats* stats);
 
 /* Prefill of ti_engine_generate's prompts (reference forward_pass, inference_engine.cpp:
  * 1429-1491): all but the last token of the shortest prompt are processed `rows` tokens at a

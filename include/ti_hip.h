@@ -547,6 +547,22 @@ int ti_sample_device_ws(const float* logits, int ldl, int M, int V, float temper
 int ti_sample_step_ws(const float* logits, int ldl, int M, int V, float temperature, int top_k, float top_p,
                       const float* draws, int draw_stride, const int32_t* step_ctr, int advance, const int32_t* n_in,
                       unsigned long long* argmax, float* logprobs, void* ws, ti_stream_t s);
+/* The lookahead verify step's form (graph-capturable; between the lm_head over the R = k + 1 rows and
+ * ti_lookahead_accept): the same kernel, one workgroup per row j of ONE stream, whose token would be the
+ * stream's new token t = state[2] (produced) + j.  state / cfg are ti_lookahead_args' words.  The row does
+ * nothing -- its argmax slots and logprobs untouched -- when state[3] (done) is set, when j > state[7] (nd: a
+ * padding row behind the step's drafts), or when t >= cfg[1] (max_new) or t >= draw_cap.  Otherwise the draw is
+ * draws[t], log p goes to logprobs[t] (nullable), and argmax[j*TI_ARGMAX_SLOTS] receives the sampled token's
+ * feedback key as in ti_sample_step, so ti_lookahead_accept, unchanged, folds row j to the sampled token and
+ * keeps draft j + 1 iff it equals it: the sequential sampler's tokens for these draws, several per step.
+ * logprobs[t] of a row the step then does not accept is rewritten by the later step that emits token t.
+ * draws, logprobs [draw_cap] (one stream's).  top_k above TI_SAMPLE_MAX_K needs ws of
+ * R * ti_sample_workspace_bytes(V, top_k) bytes.
+ * TI_ERR_ARG (nothing launched): null logits / draws / state / cfg / argmax, R outside [1, TI_LA_MAX_K + 1],
+ * V < 1, ldl < V, draw_cap < 1, top_k outside [1, V], top_k > TI_SAMPLE_MAX_K with a null ws. */
+int ti_lookahead_sample(const float* logits, int ldl, int R, int V, float temperature, int top_k, float top_p,
+                        const float* draws, int draw_cap, const int32_t* state, const int32_t* cfg,
+                        unsigned long long* argmax, float* logprobs, void* ws, ti_stream_t s);
 
 /* -------------------------------------------------------------- fp32 op level */
 /* y[r][n] (+)= sum_k a[r][k]*b[k][n], b the reference [K][N] fp32 layout, one fmaf per k

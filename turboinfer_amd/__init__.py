@@ -112,6 +112,7 @@ EXPORTED = [
     "ti_engine_generate_lookahead",
     "ti_gemm_onerow_epi_launches",
     "ti_qkv_attn_v_deferred",
+    "ti_lookahead_sample", "ti_engine_generate_lookahead_sampled", "ti_engine_serve_sampled",
 ]
 
 _lib = None
@@ -243,6 +244,11 @@ def lib() -> C.CDLL:
             L.ti_lookahead_accept.argtypes = [C.POINTER(LookaheadArgs), vp]
             L.ti_engine_generate_lookahead.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp,
                                                        C.POINTER(LookaheadStats)]
+        if hasattr(L, "ti_lookahead_sample"):   # (older TI_LIB builds in A/B runs lack the sampled device loops)
+            L.ti_lookahead_sample.argtypes = [vp, i32, i32, i32, f32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp]
+            L.ti_engine_generate_lookahead_sampled.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, f32, i32,
+                                                               f32, vp, vp, vp, C.POINTER(LookaheadStats)]
+            L.ti_engine_serve_sampled.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, i32, f32, vp, vp, vp, vp]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -505,6 +511,41 @@ class Engine:
                                                  None if cp is None or cp.size == 0 else _ptr(cp),
                                                  0 if cp is None else cp.size, k, ngram, max_new, _ptr(out), C.byref(st)))
         return out, dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted, produced=st.produced)
+
+    def generate_lookahead_sampled(self, prompt, max_new, temperature, top_k, top_p, draws, k=7, ngram=3, corpus=None,
+                                   stream=0, start_pos=0):
+        """ti_engine_generate_lookahead_sampled: the tokens generate_sampled gives one stream for the same draws
+        [max_new], k n-gram drafts verified per step -> (tokens [max_new], -1 after a stop token; logprobs
+        [max_new], 0.0 there; stats dict as generate_lookahead)."""
+        p = np.ascontiguousarray(prompt, np.int32).reshape(-1)
+        cp = None if corpus is None else np.ascontiguousarray(corpus, np.int32).reshape(-1)
+        n = max(int(max_new), 1)
+        d = None if draws is None else np.ascontiguousarray(draws, np.float32).reshape(-1)
+        if d is not None and d.size < n:
+            raise TiError(f"generate_lookahead_sampled: {d.size} draws for {n} new tokens")
+        out = np.zeros(n, np.int32)
+        lp = np.zeros(n, np.float32)
+        st = LookaheadStats()
+        check(lib().ti_engine_generate_lookahead_sampled(self.h, stream, _ptr(p), p.size, start_pos,
+                                                         None if cp is None or cp.size == 0 else _ptr(cp),
+                                                         0 if cp is None else cp.size, k, ngram, max_new, temperature,
+                                                         top_k, top_p, None if d is None else _ptr(d), _ptr(out),
+                                                         _ptr(lp), C.byref(st)))
+        return out, lp, dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted, produced=st.produced)
+
+    def serve_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, eos=2, chunk=16):
+        """ti_engine_serve_sampled (continuous batching with the device sampler): request r's t-th new token
+        takes draws[r][t] -> (each request's new tokens, each request's log-probabilities), in request order."""
+        flat = np.ascontiguousarray([t for p in prompts for t in p], np.int32)
+        offs = np.ascontiguousarray(np.cumsum([0] + [len(p) for p in prompts]), np.int32)
+        d = np.ascontiguousarray(draws, np.float32).reshape(len(prompts), max_new)
+        out = np.zeros((len(prompts), max_new), np.int32)
+        lp = np.zeros((len(prompts), max_new), np.float32)
+        n = np.zeros(len(prompts), np.int32)
+        check(lib().ti_engine_serve_sampled(self.h, len(prompts), _ptr(flat), _ptr(offs), max_new, eos, chunk,
+                                            temperature, top_k, top_p, _ptr(d), _ptr(out), _ptr(n), _ptr(lp)))
+        return ([out[r, : n[r]].tolist() for r in range(len(prompts))],
+                [lp[r, : n[r]].copy() for r in range(len(prompts))])
 
     def generate_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, start_pos=None):
         """ti_engine_generate_sampled: tokens [n][max_new] and log-probs [n][max_new]."""

@@ -51,8 +51,15 @@ int kv_bits_option(const ModelMetadata& md) {
   return b;
 }
 
-// "turboinfer.lookahead" / TI_LOOKAHEAD: n-gram drafts verified per step by a greedy request that runs alone
-// (ti_engine_generate_lookahead); 0 (the default) = off, up to 15; not with the e4m3 KV cache.
+// "turboinfer.lookahead" / TI_LOOKAHEAD: n-gram drafts verified per step by a request that runs alone, greedy
+// (ti_engine_generate_lookahead) or sampled (ti_engine_generate_lookahead_sampled); 0 (the default) = off, up to
+// 15; not with the e4m3 KV cache.
+// TI_BATCH_SAMPLE_DEVICE=0: generate_batch keeps groups of sampled requests on the host-sampler loop (A/B knob)
+bool batch_sample_device() {
+  const char* v = std::getenv("TI_BATCH_SAMPLE_DEVICE");
+  return v ? std::atoi(v) != 0 : true;
+}
+
 int lookahead_option(const ModelMetadata& md, int kv_bits) {
   const int k = engine_option(md, "turboinfer.lookahead", "TI_LOOKAHEAD", 0);
   if (k < 0 || k > TI_LA_MAX_K) throw std::runtime_error("InferenceEngine: lookahead must be 0 (off) .. 15 drafts per step");
@@ -253,7 +260,7 @@ class InferenceEngineImpl {
   ti_engine_config cfg{};
   int capacity = 1;      // streams one device call holds
   int kv_bits = 16;      // 8: e4m3 KV cache (TI_BITS_KV8 at ti_engine_create; cfg.bits stays the weight format)
-  int lookahead = 0;     // > 0: a greedy request that runs alone verifies this many n-gram drafts per step
+  int lookahead = 0;     // > 0: a request that runs alone (greedy or sampled) verifies this many n-gram drafts per step
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -652,7 +659,14 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
     // stops at EOS in chunks, so this is not the planned step count)
     uint64_t d0 = 0, p0 = 0, d1 = 0, p1 = 0;
     check(ti_engine_counters(im.eng, &d0, &p0), "ti_engine_counters");
-    const bool device_loop = greedy || (n == 1 && config_.top_k >= 1 && config_.top_k <= (size_t)V);
+    // the device sampler's range of top_k (sampled, or greedy with include_logprobs)
+    const bool sampled_k = !greedy && config_.top_k >= 1 && config_.top_k <= (size_t)V;
+    // a group of such requests runs ti_engine_generate_sampled with n streams: in lock step from position 0, so
+    // it must leave every request its budget (steps = longest prompt + new - 1 <= max_seq); otherwise, and under
+    // TI_BATCH_SAMPLE_DEVICE=0 (A/B knob), the host-sampler loop below
+    const bool sampled_group = sampled_k && n > 1 && batch_sample_device() && want <= (size_t)im.cfg.max_seq + 1 - stride &&
+                               stride <= (size_t)im.cfg.max_seq;
+    const bool device_loop = greedy || (sampled_k && (n == 1 || sampled_group));
     if (greedy) {
       // the whole token loop on the device (argmax feedback); it stops once every request of the
       // group emitted EOS (ti_engine_set_stop), the length limit is applied after
@@ -680,10 +694,12 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
         const size_t b = budget(batches[c0 + m].size());
         for (size_t t = 0; t < std::min(b, steps_new); ++t) fresh[m].push_back(out[(size_t)m * steps_new + t]);
       }
-    } else if (n == 1 && config_.top_k >= 1 && config_.top_k <= (size_t)V) {
+    } else if (sampled_k && n == 1) {
       // one request with top-k sampling (any k up to the vocabulary): the whole loop on the device
       // (ti_engine_generate_sampled), fed the engine's mt19937 draws in the reference's order;
-      // the generator then advances by the draws the request actually used (one per token)
+      // the generator then advances by the draws the request actually used (one per token).
+      // With the lookahead option and its k KV rows of head-room: the same tokens for the same draws, several
+      // per step where the text repeats itself (ti_engine_generate_lookahead_sampled; no corpus, 3-grams).
       const auto& p = batches[c0];
       const size_t steps_new = std::min(want, (size_t)im.cfg.max_seq + 1 - p.size());
       std::mt19937 saved = im.rng;
@@ -692,10 +708,18 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
       for (float& d : draws) d = dist(im.rng);
       std::vector<int32_t> prompt(p.begin(), p.end()), out(steps_new);
       const int32_t len = (int32_t)p.size();
-      check(ti_engine_generate_sampled(im.eng, 1, prompt.data(), &len, (int)p.size(), nullptr, (int)steps_new,
-                                       config_.temperature, (int)config_.top_k, config_.top_p, draws.data(), out.data(),
-                                       lp.data()),
-            "ti_engine_generate_sampled");
+      if (im.lookahead > 0 && steps_new >= 1 &&
+          p.size() + steps_new - 1 + (size_t)im.lookahead <= (size_t)im.cfg.max_seq) {
+        check(ti_engine_generate_lookahead_sampled(im.eng, 0, prompt.data(), len, 0, nullptr, 0, im.lookahead, 3,
+                                                   (int)steps_new, config_.temperature, (int)config_.top_k,
+                                                   config_.top_p, draws.data(), out.data(), lp.data(), nullptr),
+              "ti_engine_generate_lookahead_sampled");
+      } else {
+        check(ti_engine_generate_sampled(im.eng, 1, prompt.data(), &len, (int)p.size(), nullptr, (int)steps_new,
+                                         config_.temperature, (int)config_.top_k, config_.top_p, draws.data(),
+                                         out.data(), lp.data()),
+              "ti_engine_generate_sampled");
+      }
       const size_t b = budget(p.size());
       for (size_t t = 0; t < std::min(b, steps_new); ++t) {
         fresh[0].push_back(out[t]);
@@ -704,6 +728,37 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
       }
       im.rng = saved;
       im.rng.discard(fresh[0].size());
+    } else if (sampled_group) {
+      // several such requests: the same device loop with n streams.  Draws come from the engine's mt19937,
+      // steps_new per request, request-major, and the generator stays advanced by all of them.  There is no
+      // draw order to preserve for a parallel group: the reference seeds its generator from the clock and runs
+      // a batch one request after the other (inference_engine.cpp:804-828), and the host loop below already
+      // consumes draws step-major across the group.  Tokens are cut at EOS and at the budget here.
+      const size_t steps_new = want;
+      std::uniform_real_distribution<float> dist(0.0f, 1.0f);
+      std::vector<float> draws((size_t)n * steps_new), lp((size_t)n * steps_new);
+      for (float& d : draws) d = dist(im.rng);
+      std::vector<int32_t> prompts((size_t)n * stride, 0), lens(n), out((size_t)n * steps_new);
+      for (int m = 0; m < n; ++m) {
+        const auto& p = batches[c0 + m];
+        std::copy(p.begin(), p.end(), prompts.begin() + (size_t)m * stride);
+        lens[m] = (int32_t)p.size();
+      }
+      check(ti_engine_generate_sampled(im.eng, n, prompts.data(), lens.data(), (int)stride, nullptr, (int)steps_new,
+                                       config_.temperature, (int)config_.top_k, config_.top_p, draws.data(), out.data(),
+                                       lp.data()),
+            "ti_engine_generate_sampled");
+      for (int m = 0; m < n; ++m) {
+        const auto& p = batches[c0 + m];
+        const size_t b = budget(p.size());
+        for (size_t t = 0; t < std::min(b, steps_new); ++t) {
+          const int32_t tok = out[(size_t)m * steps_new + t];
+          if (tok < 0) break;   // (past the stop token)
+          fresh[m].push_back(tok);
+          if (include_logprobs) lps[m].push_back(lp[(size_t)m * steps_new + t]);
+          if (tok == kGenerateEos || p.size() + fresh[m].size() >= maxlen) break;
+        }
+      }
     } else {
       // logits to the host every step: the reference sampler (temperature / top-k / top-p / draw)
       std::vector<float> logits((size_t)n * V);

@@ -142,6 +142,11 @@ struct ti_engine {
   int32_t* la_out = nullptr;     // [la_out_cap]
   int la_hist_cap = 0, la_out_cap = 0;
   float* la_ws = nullptr;        // ti_attn_prefill_split workspace (16 rows, 32 splits)
+  // ti_engine_generate_lookahead_sampled: its verify graphs (second key word | kLaSampledKey) also bake the
+  // sampler's parameters (samp_t / samp_k / samp_p, samp_ws) and these two; a change of either drops the graphs
+  float* la_draws = nullptr;     // [la_samp_cap] the request's uniform draws, per new token
+  float* la_lps = nullptr;       // [la_samp_cap] log p of the sampled tokens
+  int la_samp_cap = 0;
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -1465,21 +1470,27 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int len, int max_
 // prompt, whose other tokens were prefilled into the slot's KV (enqueue_prefill) just before.
 // After the chunk the slots' new tokens are read back (the step feed record + the last
 // argmax); finished requests (EOS, max_new) free their slot for the next queued request.
-int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new, int eos,
-                    int chunk, int32_t* out_tokens, int32_t* out_len) {
-  if (!e || !prompts || !offsets || !out_tokens || !out_len || n_req < 1 || max_new < 1 || chunk < 1)
-    return ti_set_error(TI_ERR_ARG, "ti_engine_serve: bad arguments");
-  DeviceScope bind_(e);
+//
+// ti_engine_serve_sampled (sp != null) is the same loop with the step graph's sampler on (samp_on, set by the
+// caller around this function).  A chunk's step s is every slot's draw index s (step_ctr 0, n_in 1), so before
+// the chunk each live slot's row of the [max_batch][draw_cap] draw buffer gets its request's next draws, and
+// after it the row of log-probabilities is read back.  With sp == null nothing of this is enqueued.
+struct ServeSampler {
+  const float* draws;   // host [n_req][max_new]
+  float* out_logprobs;  // host [n_req][max_new], nullable
+};
+
+static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                      int max_new, int eos, int chunk, const ServeSampler* sp, int32_t* out_tokens, int32_t* out_len) {
   const ti_engine_config& c = e->c;
-  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_serve: compat engine");
   const int B = c.max_batch;
   const int pf = e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16);
   int max_len = 1;
   for (int r = 0; r < n_req; ++r) {
     const int L = offsets[r + 1] - offsets[r];
     if (L < 1 || L + max_new - 1 > c.max_seq)
-      return ti_set_error(TI_ERR_ARG, "ti_engine_serve: request %d: %d prompt + %d new tokens exceed max_seq %d", r, L,
-                          max_new, c.max_seq);
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, L, max_new,
+                          c.max_seq);
     max_len = std::max(max_len, L);
   }
   TI_TRY(ensure_io(e, max_len, chunk + 1));
@@ -1488,6 +1499,12 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
   std::vector<int> slot_req(B, -1), slot_pos(B, 0), slot_tok(B, 0);
   std::vector<int32_t> in((size_t)B * e->in_cap, 0), nin(B, 1), base(B, 0), outd((size_t)B * e->out_cap);
   std::vector<unsigned long long> am;
+  std::vector<float> dr, lp;
+  if (sp) {
+    dr.assign((size_t)B * e->draw_cap, 0.5f);
+    lp.resize((size_t)B * e->draw_cap);
+    if (sp->out_logprobs) std::fill(sp->out_logprobs, sp->out_logprobs + (size_t)n_req * max_new, 0.0f);
+  }
   int next = 0, live = 0;
   for (;;) {
     // admit queued requests into free slots: prefill all but the prompt's last token
@@ -1527,8 +1544,18 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
     TI_TRY(ti_memcpy_h2d(e->base_pos, base.data(), (size_t)B * 4, e->s));
     const int32_t zero = 0;
     TI_TRY(ti_memcpy_h2d(e->step_ctr, &zero, 4, e->s));
+    if (sp) {   // request r's t-th new token takes draws[r][t], whatever slot and chunk it runs in
+      for (int m = 0; m < B; ++m) {
+        const int r = slot_req[m];
+        if (r < 0) continue;
+        const int nd = std::min(S, max_new - out_len[r]);
+        std::memcpy(&dr[(size_t)m * e->draw_cap], sp->draws + (size_t)r * max_new + out_len[r], (size_t)nd * 4);
+      }
+      TI_TRY(ti_memcpy_h2d(e->draws, dr.data(), dr.size() * 4, e->s));
+    }
     TI_TRY(run_steps(e, B, 1, S));
     TI_TRY(ti_memcpy_d2h(outd.data(), e->out_tokens, outd.size() * 4, e->s));
+    if (sp && sp->out_logprobs) TI_TRY(ti_memcpy_d2h(lp.data(), e->lps, lp.size() * 4, e->s));
     TI_TRY(read_argmax(e, B, am));   // synchronises the stream
     for (int m = 0; m < B; ++m) {
       const int r = slot_req[m];
@@ -1538,6 +1565,7 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
       for (int s = 0; s < S && slot_req[m] >= 0; ++s) {
         const int32_t tok = s < S - 1 ? outd[(size_t)m * e->out_cap + s]
                                       : (int32_t)(0xFFFFFFFFu - (uint32_t)(am[m] & 0xFFFFFFFFull));
+        if (sp && sp->out_logprobs) sp->out_logprobs[(size_t)r * max_new + out_len[r]] = lp[(size_t)m * e->draw_cap + s];
         out_tokens[(size_t)r * max_new + out_len[r]++] = tok;
         slot_tok[m] = tok;
         if (out_len[r] >= max_new || tok == eos) {
@@ -1549,6 +1577,61 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
     }
   }
   return TI_OK;
+}
+
+int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new, int eos,
+                    int chunk, int32_t* out_tokens, int32_t* out_len) {
+  if (!e || !prompts || !offsets || !out_tokens || !out_len || n_req < 1 || max_new < 1 || chunk < 1)
+    return ti_set_error(TI_ERR_ARG, "ti_engine_serve: bad arguments");
+  DeviceScope bind_(e);
+  if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_serve: compat engine");
+  return serve_loop("ti_engine_serve", e, n_req, prompts, offsets, max_new, eos, chunk, nullptr, out_tokens, out_len);
+}
+
+int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new,
+                            int eos, int chunk, float temperature, int top_k, float top_p, const float* draws,
+                            int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
+  const char* fn = "ti_engine_serve_sampled";
+  if (!e || !prompts || !offsets || !draws || !out_tokens || !out_len || n_req < 1 || max_new < 1 || chunk < 1)
+    return ti_set_error(TI_ERR_ARG, "%s: bad arguments", fn);
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
+  if (top_k < 1 || top_k > c.vocab) return ti_set_error(TI_ERR_ARG, "%s: top_k %d not in [1, vocab %d]", fn, top_k, c.vocab);
+  for (int r = 0; r < n_req; ++r) {   // (before the sampler's buffers move)
+    const int L = offsets[r + 1] - offsets[r];
+    if (L < 1 || L + max_new - 1 > c.max_seq)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, L, max_new,
+                          c.max_seq);
+  }
+  // what the sampled step graphs bake in, as ti_engine_generate_sampled: a chunk needs `chunk` draws per slot
+  const size_t wsb = ti_sample_workspace_bytes(c.vocab, top_k) * (size_t)c.max_batch;
+  const bool params = e->samp_t != temperature || e->samp_k != top_k || e->samp_p != top_p;
+  if (chunk > e->draw_cap || wsb > e->samp_ws_bytes || params) {
+    TI_TRY(ti_stream_sync(e->s));
+    for (auto& g : e->graphs) hipGraphExecDestroy(g.second);
+    e->graphs.clear();
+  }
+  if (chunk > e->draw_cap) {
+    const int cap = std::max(chunk, 64);
+    TI_TRY(e->alloc_t(&e->draws, (size_t)c.max_batch * cap));
+    TI_TRY(e->alloc_t(&e->lps, (size_t)c.max_batch * cap));
+    e->draw_cap = cap;
+  }
+  if (wsb > e->samp_ws_bytes) {
+    void* p = nullptr;
+    TI_TRY(e->alloc(&p, wsb));
+    e->samp_ws = p;
+    e->samp_ws_bytes = wsb;
+  }
+  e->samp_t = temperature;
+  e->samp_k = top_k;
+  e->samp_p = top_p;
+  const ServeSampler sp{draws, out_logprobs};
+  e->samp_on = true;
+  const int rc = serve_loop(fn, e, n_req, prompts, offsets, max_new, eos, chunk, &sp, out_tokens, out_len);
+  e->samp_on = false;
+  return rc;
 }
 
 // ------------------------------------------------------------------------------ scoring
@@ -1648,7 +1731,8 @@ ti_lookahead_args la_args(ti_engine* e, int k) {
 
 // One verify step of stream slot `stream`: the draft lookup, k + 1 rows through every layer as a prompt chunk
 // (positions from the device, key-split attention), the lm_head's greedy keys, accept / commit.
-int enqueue_verify(ti_engine* e, int stream, int k, int splits) {
+// `sampled`: ti_lookahead_sample between the two turns each live row's greedy keys into its sampled token's.
+int enqueue_verify(ti_engine* e, int stream, int k, int splits, bool sampled) {
   const ti_engine_config& c = e->c;
   const int R = k + 1;
   const ti_lookahead_args a = la_args(e, k);
@@ -1660,11 +1744,16 @@ int enqueue_verify(ti_engine* e, int stream, int k, int splits) {
   el.out = e->la_logits;
   el.argmax = e->argmax;
   TI_TRY(gemm_rows(e, e->lm, R, e->h, TI_X_F32_RMSNORM, c.hidden, e->out_norm, el, 4, false));
+  if (sampled)
+    TI_TRY(ti_lookahead_sample(e->la_logits, c.vocab, R, c.vocab, e->samp_t, e->samp_k, e->samp_p, e->la_draws,
+                               e->la_samp_cap, a.state, a.cfg, e->argmax, e->la_lps, e->samp_ws, e->s));
   return ti_lookahead_accept(&a, e->s);
 }
 
-int get_verify_graph(ti_engine* e, int stream, int k, int splits, hipGraphExec_t* out) {
-  const auto key = std::make_pair(-(32 * stream + k + 1), splits);
+constexpr int kLaSampledKey = 64;   // (splits <= 32)
+
+int get_verify_graph(ti_engine* e, int stream, int k, int splits, bool sampled, hipGraphExec_t* out) {
+  const auto key = std::make_pair(-(32 * stream + k + 1), splits | (sampled ? kLaSampledKey : 0));
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) {
     *out = it->second;
@@ -1672,7 +1761,7 @@ int get_verify_graph(ti_engine* e, int stream, int k, int splits, hipGraphExec_t
   }
   TI_TRY(ti_gemm_prepare());
   E_CHECK(hipStreamBeginCapture(e->s, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
-  const int rc = enqueue_verify(e, stream, k, splits);
+  const int rc = enqueue_verify(e, stream, k, splits, sampled);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(e->s, &g);
   if (rc != TI_OK) {
@@ -1694,15 +1783,20 @@ void drop_graphs(ti_engine* e) {
   e->graphs.clear();
 }
 
-}  // namespace
+// The sampler of ti_engine_generate_lookahead_sampled (null: the greedy entry point, which enqueues nothing of it)
+struct LaSampler {
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* draws;   // host [max_new]
+  float* out_logprobs;  // host [max_new], nullable
+};
 
-extern "C" {
-
-int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
-                                 const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
-                                 int32_t* out_tokens, ti_lookahead_stats* stats) {
-  const char* fn = "ti_engine_generate_lookahead";
-  if (!e || !prompt || !out_tokens || (!corpus && corpus_len != 0)) return ti_set_error(TI_ERR_ARG, "%s: null", fn);
+int la_generate(const char* fn, ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                const int32_t* corpus, int corpus_len, int k, int ngram, int max_new, const LaSampler* sp,
+                int32_t* out_tokens, ti_lookahead_stats* stats) {
+  if (!e || !prompt || !out_tokens || (!corpus && corpus_len != 0) || (sp && !sp->draws))
+    return ti_set_error(TI_ERR_ARG, "%s: null", fn);
   DeviceScope bind_(e);
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
@@ -1713,6 +1807,8 @@ int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt
   if (k < 1 || k > TI_LA_MAX_K) return ti_set_error(TI_ERR_ARG, "%s: k %d outside [1, %d]", fn, k, TI_LA_MAX_K);
   if (ngram < 1 || ngram > TI_LA_MAX_NGRAM)
     return ti_set_error(TI_ERR_ARG, "%s: ngram %d outside [1, %d]", fn, ngram, TI_LA_MAX_NGRAM);
+  if (sp && (sp->top_k < 1 || sp->top_k > c.vocab))
+    return ti_set_error(TI_ERR_ARG, "%s: top_k %d not in [1, vocab %d]", fn, sp->top_k, c.vocab);
   for (int i = 0; i < prompt_len; ++i)
     if (prompt[i] < 0 || prompt[i] >= c.vocab)
       return ti_set_error(TI_ERR_ARG, "%s: prompt token %d at %d outside [0, vocab %d)", fn, prompt[i], i, c.vocab);
@@ -1746,6 +1842,33 @@ int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt
       e->la_out_cap = max_new;
     }
   }
+  if (sp) {
+    // what the sampled verify graphs bake in, as ti_engine_generate_sampled does for the step graphs: the draw
+    // and log-probability buffers, the sampler workspace (top_k > TI_SAMPLE_MAX_K, one row per verify row;
+    // shared with the step graphs, whose max_batch rows it must still hold) and the sampler's parameters
+    const size_t wsb = ti_sample_workspace_bytes(c.vocab, sp->top_k) * (size_t)std::max(c.max_batch, TI_LA_MAX_K + 1);
+    const bool params = e->samp_t != sp->temperature || e->samp_k != sp->top_k || e->samp_p != sp->top_p;
+    if (max_new > e->la_samp_cap || wsb > e->samp_ws_bytes || params) {
+      TI_TRY(ti_stream_sync(e->s));
+      drop_graphs(e);
+    }
+    if (max_new > e->la_samp_cap) {
+      const int scap = std::max(max_new, 64);
+      TI_TRY(e->alloc_t(&e->la_draws, (size_t)scap));
+      TI_TRY(e->alloc_t(&e->la_lps, (size_t)scap));
+      e->la_samp_cap = scap;
+    }
+    if (wsb > e->samp_ws_bytes) {
+      void* p = nullptr;
+      TI_TRY(e->alloc(&p, wsb));
+      e->samp_ws = p;
+      e->samp_ws_bytes = wsb;
+    }
+    e->samp_t = sp->temperature;
+    e->samp_k = sp->top_k;
+    e->samp_p = sp->top_p;
+    TI_TRY(ti_memcpy_h2d(e->la_draws, sp->draws, (size_t)max_new * 4, e->s));
+  }
   TI_TRY(ensure_io(e, prompt_len, 1));
   TI_TRY(ti_memcpy_h2d(e->in_tokens + (size_t)stream * e->in_cap, prompt, (size_t)prompt_len * 4, e->s));
   std::vector<int32_t> hist((size_t)corpus_len + prompt_len);
@@ -1760,7 +1883,7 @@ int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt
   for (int t0 = 0; t0 < prompt_len - 1; t0 += pf)
     TI_TRY(enqueue_prefill(e, stream, t0, std::min(pf, prompt_len - 1 - t0), start_pos));
   hipGraphExec_t g = nullptr;
-  TI_TRY(get_verify_graph(e, stream, k, la_splits(e, R), &g));
+  TI_TRY(get_verify_graph(e, stream, k, la_splits(e, R), sp != nullptr, &g));
   // replays in growing chunks (4, 8, 16, .. 64), the state read back after each; at most max_new steps.  A
   // replay after `done` changes nothing (begin writes padding rows, accept returns) but costs a whole step, a
   // read-back costs microseconds: a chunk is no longer than the steps the rest needs at the tokens per step
@@ -1778,9 +1901,33 @@ int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt
   const int produced = std::min(std::max(st[2], 0), max_new);
   if (produced) TI_TRY(ti_memcpy_d2h(out_tokens, e->la_out, (size_t)produced * 4, e->s));
   for (int t = produced; t < max_new; ++t) out_tokens[t] = -1;
+  if (sp && sp->out_logprobs) {
+    if (produced) TI_TRY(ti_memcpy_d2h(sp->out_logprobs, e->la_lps, (size_t)produced * 4, e->s));
+    for (int t = produced; t < max_new; ++t) sp->out_logprobs[t] = 0.0f;
+  }
   if (stats) *stats = ti_lookahead_stats{st[4], st[5], st[6], st[2]};
   if (!st[3]) return ti_set_error(TI_ERR_HIP, "%s: not complete after %d verify steps (produced %d of %d)", fn, ran, st[2], max_new);
   return TI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ti_engine_generate_lookahead(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                                 const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
+                                 int32_t* out_tokens, ti_lookahead_stats* stats) {
+  return la_generate("ti_engine_generate_lookahead", e, stream, prompt, prompt_len, start_pos, corpus, corpus_len, k,
+                     ngram, max_new, nullptr, out_tokens, stats);
+}
+
+int ti_engine_generate_lookahead_sampled(ti_engine* e, int stream, const int32_t* prompt, int prompt_len, int start_pos,
+                                         const int32_t* corpus, int corpus_len, int k, int ngram, int max_new,
+                                         float temperature, int top_k, float top_p, const float* draws,
+                                         int32_t* out_tokens, float* out_logprobs, ti_lookahead_stats* stats) {
+  const LaSampler sp{temperature, top_k, top_p, draws, out_logprobs};
+  return la_generate("ti_engine_generate_lookahead_sampled", e, stream, prompt, prompt_len, start_pos, corpus,
+                     corpus_len, k, ngram, max_new, &sp, out_tokens, stats);
 }
 
 int ti_engine_set_stop(ti_engine* e, int32_t token) {

@@ -282,6 +282,10 @@ __device__ __forceinline__ void stamp_end(unsigned long long* st, unsigned long 
 enum { STAMP_OTHER = 0, STAMP_GEMV = 1, STAMP_ATTN = 2, STAMP_BEGIN = 3, STAMP_ROWS = 4, STAMP_TILE = 5,
        STAMP_RMSNORM = 6, STAMP_MB = 7 };
 
+// words of ti_lookahead_args.state / .cfg (ti_hip.h): lookahead.hip, and the sampler's verify-row mode
+enum { LA_LEN = 0, LA_POS, LA_PRODUCED, LA_DONE, LA_STEPS, LA_DRAFTED, LA_ACCEPTED, LA_ND };
+enum { LA_CFG_NGRAM = 0, LA_CFG_MAX_NEW, LA_CFG_STOP, LA_CFG_CAP };
+
 }  // namespace ti
 
 // The stamp buffer slot of the next launch (host side, engine.cpp): NULL unless this thread is

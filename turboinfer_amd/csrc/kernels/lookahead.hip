@@ -8,9 +8,6 @@
 
 namespace ti {
 
-enum { LA_LEN = 0, LA_POS, LA_PRODUCED, LA_DONE, LA_STEPS, LA_DRAFTED, LA_ACCEPTED, LA_ND };
-enum { LA_CFG_NGRAM = 0, LA_CFG_MAX_NEW, LA_CFG_STOP, LA_CFG_CAP };
-
 constexpr int kLaThreads = 1024;
 
 // One workgroup per row j.  Every workgroup runs the same lookup over the history (it is read from L2 after

@@ -22,6 +22,9 @@
 // per-row HBM workspace instead of LDS (sample_kernel<true>).  Differences to the reference: exp / log are the device's (<= 1 ulp from
 // glibc), and equal logits at the k-th place / equal probabilities at the top-p cut are taken
 // lowest index first (libstdc++'s std::sort leaves their order unspecified).
+// Which draw a row takes: draws[m] (ti_sample_device), the decode loop's step counter (ti_sample_step), or, for
+// the k + 1 rows of a lookahead verify step of one stream, the stream's produced count plus the row
+// (ti_lookahead_sample: rows that are padding, past the budget or behind `done` return before the first load).
 #include <math.h>
 
 #include "common.hpp"
@@ -40,6 +43,10 @@ struct SampArgs {
   int32_t advance;             // with step_ctr / n_in: draw index t = (*step_ctr - advance) - (n_in[m] - 1)
   const int32_t* step_ctr;     // nullable: t = 0
   const int32_t* n_in;
+  // lookahead verify rows (ti_lookahead_sample), when la_state is set: row m of ONE stream is its new token
+  // t = la_state[produced] + m; draws and logprobs are that stream's [draw_stride], indexed by t alone
+  const int32_t* la_state;     // nullable
+  const int32_t* la_cfg;
   unsigned long long* argmax;  // [M][TI_ARGMAX_SLOTS], nullable: slot 0 gets the token's feedback key
   int32_t* tokens;             // [M], nullable
   float* logprobs;             // [M][lp_stride], nullable
@@ -136,9 +143,20 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
   auto lg = [&](int i) { return temp ? row[i] / a.temperature : row[i]; };
 
   int t = 0;   // which draw (and logprob slot) this step's token is
-  if (a.step_ctr) t = (*a.step_ctr - a.advance) - (a.n_in ? a.n_in[m] - 1 : 0);
+  size_t dm = (size_t)m * a.draw_stride;   // the row's draws
+  size_t lm = (size_t)m * a.lp_stride;     // and logprobs
+  if (a.la_state) {
+    // (block-uniform) a finished request, a padding row behind the step's drafts, a token past the budget:
+    // the row keeps the lm_head's greedy keys, which ti_lookahead_accept never reads
+    if (a.la_state[LA_DONE] || m > a.la_state[LA_ND]) return;
+    t = a.la_state[LA_PRODUCED] + m;
+    if (t >= a.la_cfg[LA_CFG_MAX_NEW]) return;
+    dm = lm = 0;
+  } else if (a.step_ctr) {
+    t = (*a.step_ctr - a.advance) - (a.n_in ? a.n_in[m] - 1 : 0);
+  }
   if (t < 0 || t >= a.draw_stride) return;   // a prompt step (its token is the prompt's) or past the budget
-  const float u = a.draws[(size_t)m * a.draw_stride + t];
+  const float u = a.draws[dm + t];
 
   // ---- k-th largest of per-thread keys: 8 bits per pass, most significant first; each pass
   // histograms the keys of `sweep_fn` that match the prefix so far (LDS atomics)
@@ -451,7 +469,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
   if (tid == 0) {
     const int tok = s_tok;
     if (a.tokens) a.tokens[m] = tok;
-    if (a.logprobs) a.logprobs[(size_t)m * a.lp_stride + t] = s_lp;
+    if (a.logprobs) a.logprobs[lm + t] = s_lp;
     // feedback like the greedy argmax: a key above every logit key (high word all ones)
     if (a.argmax) a.argmax[(size_t)m * TI_ARGMAX_SLOTS] = (0xFFFFFFFFull << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)tok);
   }
@@ -536,4 +554,29 @@ extern "C" int ti_sample_step(const float* logits, int ldl, int M, int V, float 
                               const int32_t* n_in, unsigned long long* argmax, float* logprobs, ti_stream_t stream) {
   return ti_sample_step_ws(logits, ldl, M, V, temperature, top_k, top_p, draws, draw_stride, step_ctr, advance, n_in,
                            argmax, logprobs, nullptr, stream);
+}
+
+extern "C" int ti_lookahead_sample(const float* logits, int ldl, int R, int V, float temperature, int top_k,
+                                   float top_p, const float* draws, int draw_cap, const int32_t* state,
+                                   const int32_t* cfg, unsigned long long* argmax, float* logprobs, void* ws,
+                                   ti_stream_t stream) {
+  ti::SampArgs a{};
+  a.ws = (char*)ws;
+  a.logits = logits;
+  a.ldl = ldl;
+  a.V = V;
+  a.top_k = top_k;
+  a.temperature = temperature;
+  a.top_p = top_p;
+  a.draws = draws;
+  a.draw_stride = draw_cap;
+  a.la_state = state;
+  a.la_cfg = cfg;
+  a.argmax = argmax;
+  a.logprobs = logprobs;
+  a.lp_stride = draw_cap;
+  if (!state || !cfg || !argmax) return ti_set_error(TI_ERR_ARG, "ti_lookahead_sample: state, cfg and argmax required");
+  if (R < 1 || R > TI_LA_MAX_K + 1)
+    return ti_set_error(TI_ERR_ARG, "ti_lookahead_sample: %d rows outside [1, %d]", R, TI_LA_MAX_K + 1);
+  return sample_launch(a, R, stream);
 }
