@@ -524,7 +524,7 @@ int ti_lookahead_accept(const ti_lookahead_args* a, ti_stream_t s);
  * (1 <= top_k <= V; above TI_SAMPLE_MAX_K with a workspace, below), softmax, top-p, the draw.  Sums run over the
  * survivors in index order (the reference's loops over V add exact zeros elsewhere); exp/log
  * are the device's, equal logits at the k-th place and equal probabilities at the top-p cut
- * go lowest index first.  One 1024-thread workgroup per stream. */
+ * go lowest index first (equal as numbers: -0.0 and +0.0 are one value).  One 1024-thread workgroup per stream. */
 #define TI_SAMPLE_MAX_K 4096
 /* logits [M][ldl] fp32, draws [M] -> tokens [M], logprobs [M] (nullable) = log p(token). */
 int ti_sample_device(const float* logits, int ldl, int M, int V, float temperature, int top_k, float top_p,

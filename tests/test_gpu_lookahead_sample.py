@@ -11,6 +11,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import sample_edge_cases as E
+
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
@@ -106,11 +108,14 @@ def test_budget_and_padding_rows_untouched(ti, oracle):
 def test_tied_logits_row(ti, oracle):
     """Row 2 holds every value twice (the second half repeats the first).  Equal logits at the k-th place go
     lowest index first on the device and wherever std::sort leaves them in the reference (test_gpu_sample.py): the
-    tied row is compared in the settings where the two agree, the other rows always."""
+    tied row is compared with the oracle in the settings where the two agree, the other rows always.  In every
+    setting the tied row is also compared with tests/sample_ref.py, which states the lowest-index rule itself: five
+    copies of it as the rows of one step, top_p placed next to p, draws[0 .. 4] = three placed draws, 0 and 1."""
     V, R = 1024, 5
     lg = seeded(R, V)
     lg[2, V // 2:] = lg[2, :V // 2]
     rig = Rig(ti, lg)
+    tied = Rig(ti, np.tile(lg[2], (R, 1)))
     agree = 0
     for T, k, p in [(1.0, 2, 1.0), (1.0, 3, 1.0), (0.7, 40, 0.9), (2.0, 7, 0.99), (0.9, 9, 1.0), (1.0, 50, 0.9),
                     (0.5, 1000, 0.5)]:
@@ -119,6 +124,15 @@ def test_tied_logits_row(ti, oracle):
         same = low == ref
         agree += same
         rig.check(oracle, T, k, p, 0, R - 1, 40, rows=None if same else {0, 1, 3, 4})
+        top_p, draws, cut, want = E.realise_row(lg[2], T, k, p)
+        assert E.decidable_cut(cut), (T, k, p, cut.top_p_margin, cut.rank_gap)
+        tied.draws_h[:R] = draws
+        tied.dd.upload(tied.draws_h)
+        keys, lps = tied.run(T, k, float(top_p), 0, R - 1, 40)
+        for j in range(R):
+            assert int(keys[j, 0]) >> 32 == 0xFFFFFFFF and np.array_equal(keys[j, 1:], tied.keys0.reshape(R, SLOTS)[j, 1:])
+            E.assert_draw(0xFFFFFFFF - (int(keys[j, 0]) & 0xFFFFFFFF), lps[j], want[j], j == R - 1, (T, k, p, j))
+        assert np.array_equal(lps[R:].view(np.uint32), np.full(CAP - R, LP_FILL, f32).view(np.uint32))
     assert agree >= 3
 
 

@@ -8,8 +8,11 @@ order exactly as the reference's loops over all V do (the rest add exact zeros).
 are the device's (<= 1 ulp from glibc), so log-probabilities agree to 1e-5 and a token could
 only differ when a draw lies within ~1e-6 of a cumulative boundary (not hit by these seeds).
 Equal logits at the top-k cut: the device keeps the lowest indices, the reference whatever
-libstdc++'s std::sort leaves there; test_device_sampler_tied_logits checks every setting where
-the two agree and counts the ones where the reference's tie order differs.
+libstdc++'s std::sort leaves there; test_device_sampler_tied_logits compares with the oracle in
+every setting where the two agree and counts the ones where the reference's tie order differs,
+and compares EVERY setting with tests/sample_ref.py, the NumPy statement of the documented tie
+rule, at a placed top_p and placed draws (tests/test_gpu_sample_edges.py has the rows made for
+that rule).
 """
 from __future__ import annotations
 
@@ -17,6 +20,8 @@ import ctypes as C
 
 import numpy as np
 import pytest
+
+import sample_edge_cases as E
 
 pytestmark = pytest.mark.gpu
 
@@ -54,8 +59,23 @@ def test_device_sampler_matches_oracle(ti, oracle, V, T, k, p):
             assert not np.isfinite(got_lp[m])
 
 
+def check_row_against_sample_ref(ti, logits, T, k, p):
+    """One row under the documented tie rule: top_p placed next to p, three placed draws, u = 0 and u = 1."""
+    top_p, draws, cut, want = E.realise_row(logits, T, k, p)
+    assert E.decidable_cut(cut), (T, k, p, cut.top_p_margin, cut.rank_gap)
+    M, V = len(draws), logits.size
+    ld, dd = dev(ti, np.tile(logits, (M, 1))), dev(ti, draws)
+    tok_d, lp_d = ti.DeviceBuffer(M * 4), ti.DeviceBuffer(M * 4)
+    ti.check(ti.lib().ti_sample_device(ld.ptr, V, M, V, T, k, float(top_p), dd.ptr, tok_d.ptr, lp_d.ptr, None))
+    ti.sync()
+    got_t, got_lp = tok_d.download(np.int32, M), lp_d.download(f32, M)
+    for m in range(M):
+        E.assert_draw(got_t[m], got_lp[m], want[m], m == M - 1, (T, k, p, m, float(draws[m]), float(top_p)))
+
+
 def test_device_sampler_tied_logits(ti, oracle):
-    """The reference's plumbing logits (every value twice: lm_head repeats every 500 columns)."""
+    """The reference's plumbing logits (every value twice: lm_head repeats every 500 columns): the oracle where
+    its tie order is the lowest indices, tests/sample_ref.py (lowest index first by definition) in every setting."""
     V = 1000
     lg = np.stack([oracle.plumbing_generate(V, 256, 4, [1, 15, 25, 35], s + 1)[1] for s in range(2)])
     ld = dev(ti, lg)
@@ -64,6 +84,8 @@ def test_device_sampler_tied_logits(ti, oracle):
                     (1.3, 0, 0.95), (0.5, 1000, 0.5)]:
         if k == 0:
             continue                                     # the device sampler needs 1 <= k
+        for row in lg:
+            check_row_against_sample_ref(ti, row, T, k, p)
         # survivors under lowest-index-first ties vs the reference's std::sort order
         low = [set(np.lexsort((np.arange(V), -row))[:k].tolist()) for row in lg]
         ref = [set(np.flatnonzero(np.isfinite(np.log(oracle.sample_probs(row, 1.0, k, 1.0)))).tolist()) for row in lg]

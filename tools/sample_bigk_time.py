@@ -26,10 +26,10 @@ for V, k, p in [(128256, 4096, 0.9), (128256, 8192, 0.9), (128256, 65536, 0.9), 
     a, b = C.c_void_p(), C.c_void_p()
     T.check(L.ti_event_create(C.byref(a)))
     T.check(L.ti_event_create(C.byref(b)))
-    T.check(L.ti_sample_device_ws(lg.ptr, V, 1, V, 0.8, k, p, dr.ptr, tok.ptr, None, None, ws.ptr))
+    T.check(L.ti_sample_device_ws(lg.ptr, V, 1, V, 0.8, k, p, dr.ptr, tok.ptr, None, ws.ptr, None))
     T.check(L.ti_event_record(a, None))
     for _ in range(50):
-        L.ti_sample_device_ws(lg.ptr, V, 1, V, 0.8, k, p, dr.ptr, tok.ptr, None, None, ws.ptr)
+        L.ti_sample_device_ws(lg.ptr, V, 1, V, 0.8, k, p, dr.ptr, tok.ptr, None, ws.ptr, None)
     T.check(L.ti_event_record(b, None))
     ms = C.c_float()
     T.check(L.ti_event_elapsed_ms(a, b, C.byref(ms)))

@@ -21,7 +21,8 @@
 // stride over the survivors; above TI_SAMPLE_MAX_K (any k up to V) the survivor arrays live in a
 // per-row HBM workspace instead of LDS (sample_kernel<true>).  Differences to the reference: exp / log are the device's (<= 1 ulp from
 // glibc), and equal logits at the k-th place / equal probabilities at the top-p cut are taken
-// lowest index first (libstdc++'s std::sort leaves their order unspecified).
+// lowest index first (libstdc++'s std::sort leaves their order unspecified); logits are equal when they compare
+// equal as numbers, so -0.0 ties with +0.0 (samp_key).
 // Which draw a row takes: draws[m] (ti_sample_device), the decode loop's step counter (ti_sample_step), or, for
 // the k + 1 rows of a lookahead verify step of one stream, the stream's produced count plus the row
 // (ti_lookahead_sample: rows that are padding, past the budget or behind `done` return before the first load).
@@ -68,9 +69,13 @@ __host__ __device__ inline int samp_pow2(int n) {
 __host__ __device__ inline size_t samp_ws_array(int V) { return ((size_t)V * 4 + 15) & ~(size_t)15; }   // 16-B aligned
 __host__ __device__ inline size_t samp_ws_row_bytes(int V) { return 5 * samp_ws_array(V) + (size_t)samp_pow2(V) * 8; }
 
+// Order-preserving key of a logit.  A negative float's key is the two's-complement negation of its pattern,
+// 0x80000000 - magnitude: descending in magnitude, below every non-negative key, and -0.0 (magnitude 0) lands on
+// +0.0's key -- the two are one value, and a tie between them goes by index like any other (with ~pattern every
+// +0.0 ranked above every -0.0).  Same instruction count as ~pattern.
 __device__ __forceinline__ uint32_t samp_key(float v) {
   const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return (u & 0x80000000u) ? 0u - u : (u | 0x80000000u);
 }
 
 // exclusive prefix sum over the block (1024 threads); also returns the total
