@@ -100,6 +100,29 @@ int ti_engine_set_stop(ti_engine* e, int32_t token);
  * (prefill) this engine has run since it was created. */
 int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_chunks);
 
+/* A prompt prefix shared by the streams of a batch (a system prompt, a few-shot header): prefilled once,
+ * attended once per step for all streams (ti_attn_decode_shared, ti_hip.h).
+ * ti_engine_share_prefix prefills tokens[0 .. n) at positions [0, n) of slot 0 as prompt chunks, copies those
+ * KV rows to slots 1 .. n_streams - 1 and registers (tokens, n, n_streams).  n == 0 clears the registration.  A
+ * call whose tokens and n_streams equal the live registration returns at once (ti_engine_counters does not
+ * move): the system-prompt cache across calls.  While registered, rows [0, n) of slots [0, n_streams) are
+ * identical and nobody writes them: an entry point that would write such a row (ti_engine_fill_kv,
+ * ti_engine_beam_search; ti_engine_generate / _generate_sampled / _score / the lookahead calls / ti_engine_step
+ * with a start position below n) clears the registration before it enqueues anything and then behaves as
+ * without one.  A change of registration drops the captured step graphs (the prefix length is baked in).
+ * Use: requests pass only their continuation as the prompt, with start_pos[m] = n.  ti_engine_generate,
+ * ti_engine_generate_sampled and ti_engine_step with 2 <= streams <= n_streams, every start position >= n and
+ * n >= TI_SHARE_MIN (environment, read when the engine is created) run their batched steps on
+ * ti_attn_decode_shared; one-stream steps and prompt chunks are as ever (each slot holds its copy).
+ * ti_engine_serve / _serve_sampled under a registration with n_streams == max_batch treat each request's prompt
+ * as the continuation behind the prefix (room: n + prompt + max_new - 1 <= max_seq; idle slots sit at position
+ * n); with fewer streams registered they clear it.
+ * TI_ERR_ARG: null e, null tokens with n > 0, n < 0, n >= max_seq, n_streams outside [2, max_batch], a token
+ * outside [0, vocab).  TI_ERR_UNSUPPORTED: a compat engine, a TI_BITS_KV8 engine. */
+int ti_engine_share_prefix(ti_engine* e, const int32_t* tokens, int n, int n_streams);
+/* The live registration's prefix length and streams (0, 0 when none); either pointer may be null. */
+int ti_engine_shared_prefix(ti_engine* e, int* len, int* n_streams);
+
 /* ti_engine_generate with the reference sampler on the device: after each
  * step's lm_head, ti_sample_step applies sample_next_token (inference_engine.cpp:1554-1673:
  * temperature, top-k, softmax, top-p, the draw) and feeds the token back, so the loop never

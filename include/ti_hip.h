@@ -430,6 +430,26 @@ int ti_attn_prefill_split(const float* q, const uint16_t* k_cache, const uint16_
  * Modes 2 and 3 apply at head_dim 128 at any grid size; other head_dims take the per-wave kernel.
  * Returns the previous mode, or -1 for a mode outside 0..3 (nothing changed). */
 int ti_attn_prefill_set_kernel(int mode);
+/* Batched decode attention over a prompt prefix the streams share (shared_attn.hip).  Layouts of q, the caches
+ * and out are ti_attn_decode's (fp16 [stream][kv_head][max_seq][head_dim], kv_stream_stride elements between
+ * streams); packed != 0 writes out as ti_attn_decode_packed does.  Stream m attends keys [0, prefix_len) of
+ * STREAM 0's cache and keys [prefix_len, pos[m]] of its own; a row with pos[m] < prefix_len - 1 attends the
+ * prefix only.  Rows [0, prefix_len) of streams >= 1 and rows past pos[m] are never read.  When every stream's
+ * prefix rows hold stream 0's values this is ti_attn_decode's function.
+ * Two dependent launches, no workgroup waits on another: (1) per (16 (stream, q-head) columns, kv-head, split)
+ * one wave attends its share of the prefix's key blocks on fp16 MFMA (the per-wave prefill kernel's arithmetic)
+ * and leaves unnormalised (acc, m, l) per column in the workspace; (2) per (stream, kv-head) the own keys with
+ * the decode kernel's arithmetic, then the prefix splits merged in split order and the own part last.
+ * Bit-reproducible from run to run.  K and V are read-only.  The workspace
+ * (ti_attn_shared_workspace_bytes, 0 outside the limits) needs no zeroing and holds no tickets.
+ * 1 <= M <= TI_ATTN_MAX_M, head_dim 64 / 128, heads / kv_heads in {1, 2, 4, 8}, 1 <= prefix_len < max_seq,
+ * 1 <= splits <= 32, packed needs heads * head_dim % 128 == 0, kv_stream_stride > 0; anything else, or a null
+ * pointer: TI_ERR_ARG, nothing launched.  Graph-capturable (no host read of pos, no allocation). */
+size_t ti_attn_shared_workspace_bytes(int M, int heads, int head_dim, int splits);
+int ti_attn_decode_shared(const float* q, const uint16_t* k_cache, const uint16_t* v_cache,
+                          int64_t kv_stream_stride, int max_seq, const int32_t* pos, int M, int heads,
+                          int kv_heads, int head_dim, int prefix_len, int splits, int packed,
+                          float* workspace, uint16_t* out, ti_stream_t s);
 
 /* The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights of this shape, e.g.
  * "gemv_wq_kernel<4,4>", "gemm_rows_kernel", "gemm_tile_kernel" (bench / profile labels). */

@@ -113,6 +113,7 @@ EXPORTED = [
     "ti_gemm_onerow_epi_launches",
     "ti_qkv_attn_v_deferred",
     "ti_lookahead_sample", "ti_engine_generate_lookahead_sampled", "ti_engine_serve_sampled",
+    "ti_attn_decode_shared", "ti_attn_shared_workspace_bytes", "ti_engine_share_prefix", "ti_engine_shared_prefix",
 ]
 
 _lib = None
@@ -249,6 +250,12 @@ def lib() -> C.CDLL:
             L.ti_engine_generate_lookahead_sampled.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, f32, i32,
                                                                f32, vp, vp, vp, C.POINTER(LookaheadStats)]
             L.ti_engine_serve_sampled.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, i32, f32, vp, vp, vp, vp]
+        if hasattr(L, "ti_attn_decode_shared"):   # (older TI_LIB builds in A/B runs lack the shared-prefix attention)
+            L.ti_attn_decode_shared.argtypes = [vp, vp, vp, C.c_int64, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+            L.ti_attn_shared_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            L.ti_attn_shared_workspace_bytes.restype = sz
+            L.ti_engine_share_prefix.argtypes = [vp, vp, i32, i32]
+            L.ti_engine_shared_prefix.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -464,6 +471,19 @@ class Engine:
         out = np.empty((self.cfg.kv_heads, n, self.cfg.head_dim), np.uint8 if kv8 else np.float16)
         check(lib().ti_engine_read_kv(self.h, layer, stream, which, pos0, n, _ptr(out)))
         return out
+
+    def share_prefix(self, tokens, n_streams):
+        """ti_engine_share_prefix: prefill `tokens` once into slot 0, copy the rows to slots 1 .. n_streams - 1 and
+        register them as the streams' common prefix (an empty `tokens` clears the registration).  Requests then
+        pass their continuation as the prompt with start_pos = len(tokens)."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        check(lib().ti_engine_share_prefix(self.h, _ptr(t) if t.size else None, t.size, n_streams))
+
+    def shared_prefix(self):
+        """(prefix length, streams) of the live registration (ti_engine_shared_prefix), (0, 0) when none."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().ti_engine_shared_prefix(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def prefill_attn_name(self, rows) -> str:
         """ti_engine_prefill_attn_name: the attention entry point a prompt chunk of `rows` rows takes on this

@@ -67,6 +67,17 @@ int lookahead_option(const ModelMetadata& md, int kv_bits) {
   return k;
 }
 
+// "turboinfer.share_prefix" / TI_SHARE_PREFIX: n > 0 -- a device-loop group of generate_batch (two or more requests)
+// whose prompts share a token prefix of at least n tokens registers it (ti_engine_share_prefix: prefilled once,
+// attended once per step for all streams) and passes the continuations; 0 (the default) = off; negative throws;
+// not with the e4m3 KV cache.
+int share_prefix_option(const ModelMetadata& md, int kv_bits) {
+  const int n = engine_option(md, "turboinfer.share_prefix", "TI_SHARE_PREFIX", 0);
+  if (n < 0) throw std::runtime_error("InferenceEngine: share_prefix must be 0 (off) or a prefix length in tokens");
+  if (n > 0 && kv_bits == 8) throw std::runtime_error("InferenceEngine: share_prefix needs the fp16 KV cache (kv_bits 16)");
+  return n;
+}
+
 [[noreturn]] void off_path(const std::string& what, const char* row) {
   throw std::runtime_error("InferenceEngine::" + what + ": not part of the MI355X decode hot path (SURVEY.md 8(f) " +
                            row + ")");
@@ -261,6 +272,7 @@ class InferenceEngineImpl {
   int capacity = 1;      // streams one device call holds
   int kv_bits = 16;      // 8: e4m3 KV cache (TI_BITS_KV8 at ti_engine_create; cfg.bits stays the weight format)
   int lookahead = 0;     // > 0: a request that runs alone (greedy or sampled) verifies this many n-gram drafts per step
+  int share_prefix = 0;  // > 0: a device-loop group whose prompts share at least this many leading tokens registers them
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -385,6 +397,7 @@ class InferenceEngineImpl {
     cfg.bits = bits == 8 || bits == 16 ? bits : 4;
     kv_bits = kv_bits_option(md);
     lookahead = lookahead_option(md, kv_bits);
+    share_prefix = share_prefix_option(md, kv_bits);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = 0;
     cfg.device = gpu;
@@ -459,6 +472,7 @@ class InferenceEngineImpl {
     cfg.bits = compat ? 16 : bits;
     kv_bits = kv_bits_option(md);
     lookahead = compat ? 0 : lookahead_option(md, kv_bits);
+    share_prefix = compat ? 0 : share_prefix_option(md, kv_bits);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = compat ? 1 : 0;
     cfg.device = gpu;
@@ -635,6 +649,28 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
   }
 
   const bool greedy = config_.top_k == 1 && !include_logprobs;
+  // The shared-prefix option: the leading tokens common to a device-loop group of two or more requests, when
+  // there are at least `share_prefix` of them, are registered (prefilled once, for every stream slot, so the next
+  // generate_batch with the same prefix finds them registered) and the group passes its continuations with
+  // start_pos = P.  Every request keeps at least one own prompt token.  The positions are those of the full
+  // prompts, so KV room, budgets and the stop handling do not change.  -> P, 0 when the group runs as ever.
+  auto share_group = [&](size_t c0, int n) -> size_t {
+    if (im.share_prefix <= 0 || n < 2) return 0;
+    const auto& a = batches[c0];
+    size_t common = a.size(), shortest = a.size();
+    for (int m = 1; m < n; ++m) {
+      const auto& b = batches[c0 + m];
+      shortest = std::min(shortest, b.size());
+      size_t k = 0;
+      while (k < common && k < b.size() && b[k] == a[k]) ++k;
+      common = k;
+    }
+    if (common < (size_t)im.share_prefix || shortest < 2) return 0;
+    const size_t P = std::min(common, shortest - 1);
+    const std::vector<int32_t> pre(a.begin(), a.begin() + (std::ptrdiff_t)P);
+    check(ti_engine_share_prefix(im.eng, pre.data(), (int)P, im.capacity), "ti_engine_share_prefix");
+    return P;
+  };
   // Requests go to the device together, `capacity` at a time.  A greedy group advances in
   // lock step from position 0, so the longest prompt bounds everyone's KV room: when that
   // would cut a request short of its budget, the group is run one request at a time.
@@ -685,6 +721,12 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
         check(ti_engine_generate_lookahead(im.eng, 0, prompts.data(), lens[0], 0, nullptr, 0, im.lookahead, 3,
                                            (int)steps_new, out.data(), nullptr),
               "ti_engine_generate_lookahead");
+      } else if (const size_t P = share_group(c0, n)) {   // the continuations behind the registered prefix
+        const std::vector<int32_t> start(n, (int32_t)P);
+        for (int m = 0; m < n; ++m) lens[m] -= (int32_t)P;
+        check(ti_engine_generate(im.eng, n, prompts.data() + P, lens.data(), (int)stride, start.data(), (int)steps_new,
+                                 out.data(), nullptr),
+              "ti_engine_generate");
       } else {
         check(ti_engine_generate(im.eng, n, prompts.data(), lens.data(), (int)stride, nullptr, (int)steps_new,
                                  out.data(), nullptr),
@@ -744,9 +786,12 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
         std::copy(p.begin(), p.end(), prompts.begin() + (size_t)m * stride);
         lens[m] = (int32_t)p.size();
       }
-      check(ti_engine_generate_sampled(im.eng, n, prompts.data(), lens.data(), (int)stride, nullptr, (int)steps_new,
-                                       config_.temperature, (int)config_.top_k, config_.top_p, draws.data(), out.data(),
-                                       lp.data()),
+      const size_t P = share_group(c0, n);   // > 0: the continuations behind the registered prefix
+      const std::vector<int32_t> start(n, (int32_t)P);
+      for (int m = 0; m < n; ++m) lens[m] -= (int32_t)P;
+      check(ti_engine_generate_sampled(im.eng, n, prompts.data() + P, lens.data(), (int)stride, P ? start.data() : nullptr,
+                                       (int)steps_new, config_.temperature, (int)config_.top_k, config_.top_p, draws.data(),
+                                       out.data(), lp.data()),
             "ti_engine_generate_sampled");
       for (int m = 0; m < n; ++m) {
         const auto& p = batches[c0 + m];

@@ -147,6 +147,15 @@ struct ti_engine {
   float* la_draws = nullptr;     // [la_samp_cap] the request's uniform draws, per new token
   float* la_lps = nullptr;       // [la_samp_cap] log p of the sampled tokens
   int la_samp_cap = 0;
+  // ti_engine_share_prefix: rows [0, share_len) of slots [0, share_n) are identical (slot 0's prefill, copied)
+  // and nobody writes them while registered.  share_use is set by ti_engine_generate / _step / the serve loop
+  // around their batched steps when these may attend the prefix once for all streams (ti_attn_decode_shared);
+  // the step-graph key carries it, and a change of registration drops the graphs (share_len is baked in).
+  std::vector<int32_t> share_tokens;
+  int share_len = 0, share_n = 0;
+  bool share_use = false;
+  int share_min = 0;             // TI_SHARE_MIN: the shortest prefix that takes the shared attention
+  float* share_ws = nullptr;     // ti_attn_decode_shared workspace (max_batch streams, 32 splits)
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -172,7 +181,7 @@ struct ti_engine {
   }
   uint16_t** kv_tab = nullptr;   // device [2 * layers]: every layer's K then V cache base (ti_kv_copy_slots)
   size_t weight_bytes = 0, kv_bytes = 0;
-  std::map<std::pair<int, int>, hipGraphExec_t> graphs;  // (M, advance | sampled << 1)
+  std::map<std::pair<int, int>, hipGraphExec_t> graphs;  // (M, advance | sampled << 1 | shared prefix << 2)
   int replay_M = 0;
 
   int qd() const { return c.heads * c.head_dim; }
@@ -362,6 +371,59 @@ int attn_partials(ti_engine* e, const uint16_t* kc, const uint16_t* vc, int M, i
   return ti_attn_decode_partials(e->q, kc, vc, e->kv_stride, c.max_seq, e->pos, M, c.heads, c.kv_heads, c.head_dim,
                                  splits, e->part_o, e->part_ml, e->s);
 }
+
+// Shared-prefix registration (ti_engine_share_prefix).  TI_SHARE_MIN: the shortest registered prefix whose
+// batched steps take ti_attn_decode_shared; shorter ones keep the plain kernel.  1024: the smallest measured
+// prefix at which 8 streams of the 7B shape win (22.6 -> 13.7 us; 256 keys 8.0 -> 10.4, 64 keys 4.4 -> 7.9); 64
+// streams win from 64 keys on, the Llama-3-8B shape at 8 streams only from 1920 (profiles/shared_prefix_ab.txt).
+#ifndef TI_SHARE_MIN_DEFAULT
+#define TI_SHARE_MIN_DEFAULT 1024
+#endif
+int share_min_env() {
+  const char* v = getenv("TI_SHARE_MIN");
+  return v && atoi(v) > 0 ? atoi(v) : TI_SHARE_MIN_DEFAULT;
+}
+// Splits of the prefix per (16 columns, kv-head), TI_SHARE_SPLITS sets them: about 512 waves (two per CU), at most
+// 8 splits, at least 4 key blocks per split -- the fastest of 1 .. 32 splits at 8 and 64 streams of the 7B and
+// the Llama-3-8B shape with 1024 and 1920 prefix keys (8, 4, 8, 4), the fastest at 64 keys and within 8 % of it at 256
+// (profiles/shared_prefix_ab.txt; more, shorter splits lose to the partials they write and the merge reads)
+int share_splits(const ti_engine* e, int M) {
+  const ti_engine_config& c = e->c;
+  const char* v = getenv("TI_SHARE_SPLITS");
+  const int nkb = (e->share_len + 15) / 16, blocks = (M * (c.heads / c.kv_heads) + 15) / 16 * c.kv_heads;
+  if (v && atoi(v) > 0) return std::min(atoi(v), std::min(32, nkb));
+  return std::max(1, std::min((512 + blocks - 1) / blocks, std::min(8, nkb / 4)));
+}
+// Forget the registration (an entry point is about to write a prefix row, or the caller asked): the graphs
+// that bake the prefix length go with it.  Nothing happens -- nothing is enqueued -- without a registration.
+int share_clear(ti_engine* e) {
+  if (e->share_len == 0) return TI_OK;
+  TI_TRY(ti_stream_sync(e->s));
+  for (auto& g : e->graphs) hipGraphExecDestroy(g.second);
+  e->graphs.clear();
+  e->share_len = e->share_n = 0;
+  e->share_tokens.clear();
+  return TI_OK;
+}
+// May M streams starting at base[0 .. M) attend the registered prefix once for all?  Clears the registration
+// first when one of them would write a prefix row of a registered slot.
+int share_begin(ti_engine* e, int M, const int32_t* base, bool* use) {
+  *use = false;
+  if (e->share_len == 0) return TI_OK;
+  bool below = false, all = true;
+  for (int m = 0; m < M; ++m) {
+    below = below || (m < e->share_n && base[m] < e->share_len);
+    all = all && base[m] >= e->share_len;
+  }
+  if (below) return share_clear(e);
+  *use = all && M >= 2 && M <= e->share_n && e->share_len >= e->share_min;
+  return TI_OK;
+}
+struct ShareScope {   // share_use for the duration of an entry point's steps
+  ti_engine* e;
+  ShareScope(ti_engine* e_, bool on) : e(e_) { e->share_use = on; }
+  ~ShareScope() { e->share_use = false; }
+};
 
 int get_graph(ti_engine* e, int M, int advance, hipGraphExec_t* out);
 
@@ -560,7 +622,11 @@ int enqueue_step(ti_engine* e, int M, int advance) {
       stamp_tag(TI_STAMP_TAG_QKV);
       TI_TRY(gemm(L.qkv, e->h, TI_X_F32_RMSNORM, H, 4, L.attn_norm, ep, 4, false));
       stamp_tag(TI_STAMP_TAG_ATTN);
-      TI_TRY(attn_merged(e, pk, L.kc, L.vc, e->kv_stride, M, e->splits_for(M)));
+      if (e->share_use)   // the registered prefix from slot 0 once for all streams, then each stream's own keys
+        TI_TRY(ti_attn_decode_shared(e->q, L.kc, L.vc, e->kv_stride, c.max_seq, e->pos, M, c.heads, c.kv_heads, c.head_dim,
+                                     e->share_len, share_splits(e, M), pk ? 1 : 0, e->share_ws, e->attn, e->s));
+      else
+        TI_TRY(attn_merged(e, pk, L.kc, L.vc, e->kv_stride, M, e->splits_for(M)));
       stamp_tag(TI_STAMP_TAG_O);
       TI_TRY(gemm(L.o, e->attn, pk ? TI_X_F16_PACKED : TI_X_F16, qd, 2, nullptr, eo, 4, false));
     }
@@ -731,7 +797,7 @@ int enqueue_prefill_layers(ti_engine* e, int m, int rows, int split_attn) {
 }
 
 int get_graph(ti_engine* e, int M, int advance, hipGraphExec_t* out) {
-  auto key = std::make_pair(M, advance | (e->samp_on ? 2 : 0));
+  auto key = std::make_pair(M, advance | (e->samp_on ? 2 : 0) | (e->share_use ? 4 : 0));
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) {
     *out = it->second;
@@ -855,6 +921,7 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
       return fail(rc);
     if (const char* env = getenv("TI_FOLD")) e->fold_on = atoi(env) != 0;
     if (const char* env = getenv("TI_QKV_ATTN")) e->qa_on = atoi(env) != 0;
+    e->share_min = share_min_env();
     if ((c.bits & ~TI_BITS_G32) == 4) {   // batched rows and prompt chunks: split-K tile GEMM (TI_SPLITK_MB, 0 = off)
       const char* env = getenv("TI_SPLITK_MB");
       const size_t mb = env ? (size_t)std::max(0, atoi(env)) : 64;
@@ -1045,6 +1112,7 @@ int ti_engine_fill_kv(ti_engine* e, int stream, int n, uint64_t seed) {
   DeviceScope bind_(e);
   if (stream < 0 || stream >= e->c.max_batch || n < 0 || n > e->c.max_seq)
     return ti_set_error(TI_ERR_ARG, "ti_engine_fill_kv: stream %d n %d", stream, n);
+  if (stream < e->share_n && n > 0) TI_TRY(share_clear(e));   // (writes the slot's rows from 0)
   for (int l = 0; l < e->c.layers; ++l) {
     DevLayer& L = e->layer[l];
     uint16_t* caches[2] = {e->kv_at(L.kc, (size_t)stream * e->kv_stride), e->kv_at(L.vc, (size_t)stream * e->kv_stride)};
@@ -1096,6 +1164,9 @@ int ti_engine_generate(ti_engine* e, int n, const int32_t* prompts, const int32_
     if (base[m] < 0 || base[m] + steps > c.max_seq)
       return ti_set_error(TI_ERR_ARG, "ti_engine_generate: stream %d needs %d KV slots > max_seq %d", m, base[m] + steps,
                           c.max_seq);
+  bool shared = false;   // a registered prefix: cleared when a start position lies inside it, else used
+  TI_TRY(share_begin(e, n, base.data(), &shared));
+  const ShareScope share_(e, shared);
   TI_TRY(ensure_io(e, stride, std::max(steps, 1)));
   std::vector<int32_t> in((size_t)n * e->in_cap, 0);
   for (int m = 0; m < n; ++m) std::memcpy(&in[(size_t)m * e->in_cap], prompts + (size_t)m * stride, (size_t)lens[m] * 4);
@@ -1344,6 +1415,7 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int len, int max_
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_beam_search: compat engine");
   if (len + max_new - 1 > c.max_seq)
     return ti_set_error(TI_ERR_ARG, "ti_engine_beam_search: %d + %d tokens exceed max_seq %d", len, max_new, c.max_seq);
+  TI_TRY(share_clear(e));   // (the beams' slots are rewritten from row 0)
   // More beams than stream slots: every candidate's next-token logits come from a full pass over
   // its sequence in slot 0 (prefill + one step), as the reference recomputes each candidate
   // (:1961) -- slower, same decisions.
@@ -1485,14 +1557,20 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
   const ti_engine_config& c = e->c;
   const int B = c.max_batch;
   const int pf = e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16);
+  // A prefix registered for every slot (ti_engine_share_prefix with n_streams == max_batch): each prompt is the
+  // continuation behind it, every slot -- idle ones too -- sits at or past P and never touches its copy of the
+  // prefix, so a freed slot is reused without a new copy.  Registered for fewer slots: cleared.  P = 0: as ever.
+  if (e->share_len > 0 && e->share_n != B) TI_TRY(share_clear(e));
+  const int P = e->share_len;
   int max_len = 1;
   for (int r = 0; r < n_req; ++r) {
     const int L = offsets[r + 1] - offsets[r];
-    if (L < 1 || L + max_new - 1 > c.max_seq)
-      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, L, max_new,
+    if (L < 1 || P + L + max_new - 1 > c.max_seq)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, P + L, max_new,
                           c.max_seq);
     max_len = std::max(max_len, L);
   }
+  const ShareScope share_(e, P > 0 && B >= 2 && P >= e->share_min);
   TI_TRY(ensure_io(e, max_len, chunk + 1));
   for (int i = 0; i < n_req * max_new; ++i) out_tokens[i] = -1;
   for (int r = 0; r < n_req; ++r) out_len[r] = 0;
@@ -1513,7 +1591,7 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
       if (slot_req[m] < 0) {
         const int r = next++, L = offsets[r + 1] - offsets[r];
         slot_req[m] = r;
-        slot_pos[m] = L - 1;
+        slot_pos[m] = P + L - 1;
         slot_tok[m] = prompts[offsets[r] + L - 1];
         fresh.push_back(m);
         ++live;
@@ -1527,14 +1605,14 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
       TI_TRY(ti_memcpy_h2d(e->in_tokens, in.data(), in.size() * 4, e->s));
       for (int m : fresh) {
         const int L = offsets[slot_req[m] + 1] - offsets[slot_req[m]];
-        for (int t0 = 0; t0 < L - 1; t0 += pf) TI_TRY(enqueue_prefill(e, m, t0, std::min(pf, L - 1 - t0), 0));
+        for (int t0 = 0; t0 < L - 1; t0 += pf) TI_TRY(enqueue_prefill(e, m, t0, std::min(pf, L - 1 - t0), P));
       }
     }
     // one chunk: every slot feeds one token at its position; no slot may run past max_seq
     int S = chunk;
     for (int m = 0; m < B; ++m) {
       nin[m] = 1;
-      base[m] = slot_req[m] >= 0 ? slot_pos[m] : 0;
+      base[m] = slot_req[m] >= 0 ? slot_pos[m] : P;
       in[(size_t)m * e->in_cap] = slot_req[m] >= 0 ? slot_tok[m] : 0;
       if (slot_req[m] >= 0) S = std::min(S, c.max_seq - slot_pos[m]);
     }
@@ -1658,6 +1736,7 @@ int ti_engine_score(ti_engine* e, int stream, const int32_t* tokens, int n, int 
     if (targets[i] < -1 || targets[i] >= c.vocab)
       return ti_set_error(TI_ERR_ARG, "ti_engine_score: target %d at %d outside [-1, vocab %d)", targets[i], i, c.vocab);
   }
+  if (stream < e->share_n && start_pos < e->share_len) TI_TRY(share_clear(e));
   if (!e->sc_logits) {
     TI_TRY(e->alloc_t(&e->sc_logits, (size_t)TI_SCORE_ROWS * c.vocab));
     TI_TRY(e->alloc_t(&e->sc_targets, (size_t)c.max_seq));
@@ -1822,6 +1901,7 @@ int la_generate(const char* fn, ti_engine* e, int stream, const int32_t* prompt,
   const int64_t cap64 = (int64_t)corpus_len + prompt_len + max_new;
   if (cap64 > (1 << 28)) return ti_set_error(TI_ERR_ARG, "%s: history of %lld tokens", fn, (long long)cap64);
   const int cap = (int)cap64, R = k + 1;
+  if (stream < e->share_n && start_pos < e->share_len) TI_TRY(share_clear(e));
 
   if (!e->la_logits) {
     TI_TRY(e->alloc_t(&e->la_logits, (size_t)(TI_LA_MAX_K + 1) * c.vocab));
@@ -1930,6 +2010,48 @@ int ti_engine_generate_lookahead_sampled(ti_engine* e, int stream, const int32_t
                      corpus_len, k, ngram, max_new, &sp, out_tokens, stats);
 }
 
+int ti_engine_share_prefix(ti_engine* e, const int32_t* tokens, int n, int n_streams) {
+  const char* fn = "ti_engine_share_prefix";
+  if (!e || (!tokens && n > 0)) return ti_set_error(TI_ERR_ARG, "%s: null", fn);
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
+  if (e->kv8) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: TI_BITS_KV8 engine (no e4m3 shared-prefix attention)", fn);
+  if (n < 0 || n >= c.max_seq) return ti_set_error(TI_ERR_ARG, "%s: n %d outside [0, max_seq %d)", fn, n, c.max_seq);
+  if (n == 0) return share_clear(e);
+  if (n_streams < 2 || n_streams > c.max_batch)
+    return ti_set_error(TI_ERR_ARG, "%s: n_streams %d outside [2, max_batch %d]", fn, n_streams, c.max_batch);
+  for (int i = 0; i < n; ++i)
+    if (tokens[i] < 0 || tokens[i] >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "%s: token %d at %d outside [0, vocab %d)", fn, tokens[i], i, c.vocab);
+  // the live registration again (the system-prompt cache across calls): nothing to do
+  if (n == e->share_len && n_streams == e->share_n && std::equal(tokens, tokens + n, e->share_tokens.begin())) return TI_OK;
+  TI_TRY(share_clear(e));
+  if (!e->share_ws) {
+    void* w = nullptr;
+    TI_TRY(e->alloc(&w, ti_attn_shared_workspace_bytes(c.max_batch, c.heads, c.head_dim, 32)));
+    e->share_ws = static_cast<float*>(w);
+  }
+  TI_TRY(ensure_io(e, n, 1));
+  TI_TRY(ti_memcpy_h2d(e->in_tokens, tokens, (size_t)n * 4, e->s));   // slot 0's token row
+  // (the chunk of ti_engine_set_prefill; when that is 0, the chunk ti_engine_serve uses)
+  const int pf = e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16);
+  for (int t0 = 0; t0 < n; t0 += pf) TI_TRY(enqueue_prefill(e, 0, t0, std::min(pf, n - t0), 0));
+  for (int d = 1; d < n_streams; ++d) TI_TRY(fork_slot(e, 0, d, n));
+  TI_TRY(ti_stream_sync(e->s));
+  e->share_tokens.assign(tokens, tokens + n);
+  e->share_len = n;
+  e->share_n = n_streams;
+  return TI_OK;
+}
+
+int ti_engine_shared_prefix(ti_engine* e, int* len, int* n_streams) {
+  if (!e) return ti_set_error(TI_ERR_ARG, "ti_engine_shared_prefix: null");
+  if (len) *len = e->share_len;
+  if (n_streams) *n_streams = e->share_n;
+  return TI_OK;
+}
+
 int ti_engine_set_stop(ti_engine* e, int32_t token) {
   if (!e || token < -1 || token >= e->c.vocab) return ti_set_error(TI_ERR_ARG, "ti_engine_set_stop: token %d", token);
   e->stop_token = token;
@@ -1969,6 +2091,9 @@ int ti_engine_step(ti_engine* e, int n, const int32_t* tokens, const int32_t* po
   if (n < 1 || n > c.max_batch) return ti_set_error(TI_ERR_ARG, "ti_engine_step: n=%d", n);
   for (int m = 0; m < n; ++m)
     if (pos[m] < 0 || pos[m] >= c.max_seq) return ti_set_error(TI_ERR_ARG, "ti_engine_step: pos %d", pos[m]);
+  bool shared = false;
+  TI_TRY(share_begin(e, n, pos, &shared));
+  const ShareScope share_(e, shared);
   TI_TRY(ensure_io(e, 1, 1));
   std::vector<int32_t> in((size_t)n * e->in_cap, 0), one(n, 1);
   for (int m = 0; m < n; ++m) in[(size_t)m * e->in_cap] = tokens[m];
@@ -2021,6 +2146,7 @@ int ti_engine_replay_prepare(ti_engine* e, int n, int kv_len, int start_token) {
   const ti_engine_config& c = e->c;
   if (n < 1 || n > c.max_batch || kv_len < 1 || kv_len > c.max_seq || start_token < 0 || start_token >= c.vocab)
     return ti_set_error(TI_ERR_ARG, "ti_engine_replay_prepare: n=%d kv_len=%d", n, kv_len);
+  if (kv_len - 1 < e->share_len) TI_TRY(share_clear(e));
   TI_TRY(ensure_io(e, 1, 1));
   std::vector<int32_t> base(n, kv_len - 1), zero(n, 0);
   std::vector<unsigned long long> am((size_t)n * TI_ARGMAX_SLOTS, 0ull);
@@ -2088,6 +2214,7 @@ int ti_engine_time_kernel(ti_engine* e, int which, int n, int kv_len, int reps, 
   if (!e || e->c.compat || !avg_us || !bytes || reps < 1 || n < 1 || n > e->c.max_batch || e->c.layers < 1)
     return ti_set_error(TI_ERR_ARG, "ti_engine_time_kernel: bad arguments");
   DeviceScope bind_(e);
+  TI_TRY(share_clear(e));   // (the timed QKV launches append at whatever positions the last call left)
   const ti_engine_config& c = e->c;
   const int H = c.hidden, I = c.inter, qd = e->qd(), kvd = e->kvd();
   const bool fold = fold_usable(e, n), part = part_usable(e, n), bfold = !fold && bfold_usable(e, n);
