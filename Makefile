@@ -49,6 +49,11 @@ $(BUILD)/k_logprob.o: turboinfer_amd/csrc/kernels/logprob.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@
 
+# penalty: one rounding per step of llama.cpp's penalty arithmetic (a NumPy float32 restatement pins it)
+$(BUILD)/k_penalty.o: turboinfer_amd/csrc/kernels/penalty.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@
+
 $(BUILD)/k_%.o: turboinfer_amd/csrc/kernels/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@

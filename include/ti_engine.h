@@ -134,6 +134,36 @@ int ti_engine_generate_sampled(ti_engine* e, int n_streams, const int32_t* promp
                                int prompt_stride, const int32_t* start_pos, int max_new, float temperature,
                                int top_k, float top_p, const float* draws, int32_t* out_tokens, float* out_logprobs);
 
+/* Repetition, presence and frequency penalties of the sampled device loops (no reference counterpart: its
+ * GenerationConfig has none; the arithmetic is llama.cpp's llama_sampler_penalties_apply with
+ * penalty_last_n = -1, ti_hip.h ti_penalty_step).  Engine state, like ti_engine_set_stop.  A stream's context
+ * is the token sequence its request has consumed so far: the prompt, then its generated tokens; count[v] is
+ * the number of occurrences of v in it, with no window.  Before the sampler sees a row of raw logits (before
+ * temperature), every token with count[v] > 0 is rewritten:
+ *   a = l <= 0 ? l * repetition : l / repetition;  out = a - (float(count) * frequency + presence)
+ * each step rounded once to fp32.  (1, 0, 0), the default, means off: the engine then enqueues exactly what
+ * it does without this call.  While the values differ from (1, 0, 0) the penalties are active:
+ *   ti_engine_generate_sampled: the context is the prompt as passed (whether its tokens run as prompt chunks
+ *     or decode steps), then the stream's new tokens.  Under a live ti_engine_share_prefix registration a
+ *     stream with start_pos == the prefix length has the registered prefix tokens at the head of its context,
+ *     so a registered run penalises what the unregistered run of the full prompts would.  With any other
+ *     start_pos > 0 only the tokens passed count: the engine does not know what the slot's earlier KV rows were.
+ *   ti_engine_serve_sampled: the request's prompt (behind the registered prefix when the loop treats prompts
+ *     as continuations), then its new tokens, whatever slot and chunk they run in; a slot freed by one
+ *     request starts empty for the next.
+ *   top_k = 1 through either is greedy decoding with penalties.
+ *   ti_engine_generate, ti_engine_serve, both lookahead calls and ti_engine_beam_search produce tokens and
+ *     cannot penalise: TI_ERR_UNSUPPORTED, naming the function, before anything is enqueued.
+ *   ti_engine_step, ti_engine_score, the replay / timing entry points return the model's own numbers.
+ * The values and the state buffers (token counts and distinct-token lists for max_batch slots, a context
+ * upload scratch, the serve loop's carry row; allocated on the first activation, outside what
+ * ti_engine_memory reports) are baked into the step graphs: a change of values drops the captured graphs.
+ * TI_ERR_ARG: null e, repetition not finite and > 0, presence or frequency not finite.
+ * TI_ERR_UNSUPPORTED: a compat engine. */
+int ti_engine_set_penalties(ti_engine* e, float repetition, float presence, float frequency);
+/* The values in force ((1, 0, 0) when never set); any pointer may be null. */
+int ti_engine_get_penalties(ti_engine* e, float* repetition, float* presence, float* frequency);
+
 /* InferenceEngine::generate_beam_search (inference_engine.cpp:830-871, 1912-2069): the
  * reference's beam loop (max-heap on log-probability, expansion by the beam_size most probable
  * tokens after temperature / softmax / top-k / top-p renormalisation (:1798-1910), length-
@@ -340,6 +370,13 @@ int ti_rope_table(const float* pos, int npos, int head_dim, float theta, float* 
  * supplied: temperature, top-k (std::sort ranking, reference tie order), softmax, top-p. */
 int ti_sample_token(const float* logits, int vocab, float temperature, int top_k, float top_p, float u,
                     int* token, float* logprob);
+/* The penalties of ti_engine_set_penalties on the host, bit for bit the device's arithmetic (ti_hip.h
+ * ti_penalty_step), for callers' own loops over ti_engine_step + ti_sample_token: logits [vocab] is rewritten
+ * in place at every token that occurs in context[0 .. n) (ids outside [0, vocab) are ignored); all other
+ * elements, and every element under (1, 0, 0), keep their bits.  TI_ERR_ARG: null logits, vocab < 1, n < 0,
+ * null context with n > 0, repetition not finite and > 0, presence or frequency not finite. */
+int ti_penalize_logits(float* logits, int vocab, const int32_t* context, int n, float repetition, float presence,
+                       float frequency);
 
 #ifdef __cplusplus
 }

@@ -584,6 +584,53 @@ int ti_lookahead_sample(const float* logits, int ldl, int R, int V, float temper
                         const float* draws, int draw_cap, const int32_t* state, const int32_t* cfg,
                         unsigned long long* argmax, float* logprobs, void* ws, ti_stream_t s);
 
+/* ------------------------------------- repetition / presence / frequency penalties
+ * llama.cpp's llama_sampler_penalties_apply over a stream's whole context (penalty_last_n = -1), applied to a
+ * row of raw fp32 logits before the sampler sees it.  Every token v with count[v] > 0 is rewritten, each step
+ * rounded once to fp32 and never contracted (IEEE division):
+ *   a = l <= 0 ? l * repetition : l / repetition;  b = float(count) * frequency;  d = b + presence;  out = a - d
+ * All other elements keep their bits.  State per stream slot, device memory owned by the caller:
+ *   counts [M][V] occurrences of each token in the slot's context
+ *   seen   [M][V] the distinct tokens of the context, in any order (capacity V: it cannot overflow)
+ *   n_seen [M]    how many of them
+ * ti_penalty_reset sets slot m to the histogram of tokens_dev[0 .. n) (device ids; n = 0 empties the slot; other
+ * slots are untouched): the slot's two rows are cleared, duplicates counted with atomics, a token appended to
+ * seen exactly when its count leaves 0; ids outside [0, V) are skipped.  Not meant for graph capture.
+ * TI_ERR_ARG (nothing enqueued): a null state pointer, V < 1, m < 0, n < 0, null tokens_dev with n > 0. */
+typedef struct ti_penalty_state {
+  int32_t* counts;
+  int32_t* seen;
+  int32_t* n_seen;
+} ti_penalty_state;
+int ti_penalty_reset(const ti_penalty_state* st, int V, int m, const int32_t* tokens_dev, int n, ti_stream_t s);
+/* The decode loop's form (graph-capturable; between the lm_head and ti_sample_step, one workgroup per stream).
+ * Stream m's draw index is ti_sample_step's: t = (*step_ctr - advance) - (n_in[m] - 1), t = 0 with a null
+ * step_ctr (n_in null: 1).  With t < 0 or t >= draw_stride the row does nothing: logits and state keep their
+ * bits.  Otherwise the row first notes the token this step fed when that token is a generated one -- for
+ * t >= 1 out_tokens[m*out_stride + t - 1], which this step's ti_step_begin recorded; for t == 0 carry[m] when
+ * carry is non-null and carry[m] >= 0 (the serve loop: every chunk restarts at step 0 with the previous
+ * chunk's last token as its input) -- incrementing its count and appending it to seen if it is new, and then,
+ * behind a workgroup barrier, walks seen[m][0 .. n_seen[m]) and rewrites logits[m*ldl + v] in place:
+ * O(distinct tokens), no element with count 0 and no column >= V touched.  n_seen is clamped to V and ids
+ * outside [0, V) are skipped, so a slot whose state was never reset cannot index out of bounds.
+ * TI_ERR_ARG (nothing launched): null args / logits / counts / seen / n_seen, null out_tokens with a step_ctr,
+ * M < 1, V < 1, ldl < V, draw_stride < 1, out_stride < 0, repetition not finite and > 0, presence or
+ * frequency not finite. */
+typedef struct ti_penalty_args {
+  float* logits;               /* [M][ldl] */
+  int32_t ldl, M, V;
+  ti_penalty_state state;
+  float repetition, presence, frequency;
+  int32_t draw_stride;
+  int32_t advance;
+  const int32_t* step_ctr;     /* nullable: t = 0 */
+  const int32_t* n_in;         /* [M], nullable: 1 */
+  const int32_t* out_tokens;   /* [M][out_stride], ti_step_args' feed record */
+  int32_t out_stride;
+  const int32_t* carry;        /* [M], nullable */
+} ti_penalty_args;
+int ti_penalty_step(const ti_penalty_args* a, ti_stream_t s);
+
 /* -------------------------------------------------------------- fp32 op level */
 /* y[r][n] (+)= sum_k a[r][k]*b[k][n], b the reference [K][N] fp32 layout, one fmaf per k
  * in ascending order (bit-identical to matmul_3d_2d).  mode: 0 store, 1 relu(store),

@@ -29,6 +29,10 @@
 //     reference's test programs) build the engine's seeded synthetic INT4 model of that shape
 //     (ti_engine_synth; the reference runs such a model on its placeholder fallbacks); without it
 //     such a ModelData throws std::runtime_error.
+//   * "turboinfer.repetition_penalty" / TI_REPETITION_PENALTY (default 1), "turboinfer.presence_penalty" /
+//     TI_PRESENCE_PENALTY, "turboinfer.frequency_penalty" / TI_FREQUENCY_PENALTY (default 0): penalties over each
+//     request's whole context (ti_engine_set_penalties); generate / generate_batch then take the
+//     sampled device loop, beam search throws; no number, a repetition <= 0, or lookahead as well: throws.
 // TensorEngine binds the device TI_GPU_INDEX names (default 0).
 //
 // Model forms accepted (reference weight names, inference_engine.cpp:483-563):

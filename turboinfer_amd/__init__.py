@@ -73,6 +73,20 @@ class LookaheadStats(C.Structure):
     _fields_ = [("steps", C.c_int32), ("drafted", C.c_int32), ("accepted", C.c_int32), ("produced", C.c_int32)]
 
 
+class PenaltyState(C.Structure):
+    """ti_penalty_state (include/ti_hip.h): device pointers counts [M][V], seen [M][V], n_seen [M], all int32."""
+    _fields_ = [("counts", C.c_void_p), ("seen", C.c_void_p), ("n_seen", C.c_void_p)]
+
+
+class PenaltyArgs(C.Structure):
+    """ti_penalty_args (include/ti_hip.h)."""
+    _fields_ = [("logits", C.c_void_p), ("ldl", C.c_int32), ("M", C.c_int32), ("V", C.c_int32),
+                ("state", PenaltyState), ("repetition", C.c_float), ("presence", C.c_float),
+                ("frequency", C.c_float), ("draw_stride", C.c_int32), ("advance", C.c_int32),
+                ("step_ctr", C.c_void_p), ("n_in", C.c_void_p), ("out_tokens", C.c_void_p),
+                ("out_stride", C.c_int32), ("carry", C.c_void_p)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("inter", C.c_int32),
@@ -114,6 +128,7 @@ EXPORTED = [
     "ti_qkv_attn_v_deferred",
     "ti_lookahead_sample", "ti_engine_generate_lookahead_sampled", "ti_engine_serve_sampled",
     "ti_attn_decode_shared", "ti_attn_shared_workspace_bytes", "ti_engine_share_prefix", "ti_engine_shared_prefix",
+    "ti_penalty_reset", "ti_penalty_step", "ti_penalize_logits", "ti_engine_set_penalties", "ti_engine_get_penalties",
 ]
 
 _lib = None
@@ -256,6 +271,12 @@ def lib() -> C.CDLL:
             L.ti_attn_shared_workspace_bytes.restype = sz
             L.ti_engine_share_prefix.argtypes = [vp, vp, i32, i32]
             L.ti_engine_shared_prefix.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "ti_penalty_step"):   # (older TI_LIB builds in A/B runs lack the penalties)
+            L.ti_penalty_reset.argtypes = [C.POINTER(PenaltyState), i32, i32, vp, i32, vp]
+            L.ti_penalty_step.argtypes = [C.POINTER(PenaltyArgs), vp]
+            L.ti_penalize_logits.argtypes = [vp, i32, vp, i32, f32, f32, f32]
+            L.ti_engine_set_penalties.argtypes = [vp, f32, f32, f32]
+            L.ti_engine_get_penalties.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -408,6 +429,17 @@ def sample_token(logits, temperature=1.0, top_k=1, top_p=0.9, u=0.5):
     t, lp = C.c_int(), C.c_float()
     check(lib().ti_sample_token(_ptr(lg), lg.size, temperature, top_k, top_p, u, C.byref(t), C.byref(lp)))
     return t.value, lp.value
+
+
+def penalize_logits(logits, context, repetition=1.0, presence=0.0, frequency=0.0) -> np.ndarray:
+    """The product's host penalties (ti_penalize_logits, bit for bit the device loops' arithmetic): a float32 copy
+    of `logits` [vocab] with every token that occurs in `context` rewritten, a = l <= 0 ? l * repetition :
+    l / repetition, out = a - (count * frequency + presence); (1, 0, 0) returns the bits unchanged."""
+    lg = np.array(logits, np.float32).reshape(-1)
+    ctx = np.ascontiguousarray(context, np.int32).reshape(-1)
+    check(lib().ti_penalize_logits(_ptr(lg), lg.size, _ptr(ctx) if ctx.size else None, ctx.size, repetition, presence,
+                                   frequency))
+    return lg
 
 
 def logprob_rows(logits: DeviceBuffer, ld: int, rows: int, vocab: int, targets: DeviceBuffer,
@@ -614,6 +646,18 @@ class Engine:
         """Stop token of generate / generate_sampled (-1: none): the device loop ends in chunks once
         every stream has emitted it (ti_engine_set_stop)."""
         check(lib().ti_engine_set_stop(self.h, token))
+
+    def set_penalties(self, repetition=1.0, presence=0.0, frequency=0.0):
+        """Repetition / presence / frequency penalties of generate_sampled and serve_sampled over each stream's whole
+        context (ti_engine_set_penalties; llama.cpp's arithmetic).  (1, 0, 0) is off.  While active, generate, serve,
+        the lookahead calls and beam_search raise ti error 3; step and score stay unpenalised."""
+        check(lib().ti_engine_set_penalties(self.h, repetition, presence, frequency))
+
+    def penalties(self):
+        """(repetition, presence, frequency) in force (ti_engine_get_penalties)."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        check(lib().ti_engine_get_penalties(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def counters(self):
         """(decode step-graph replays, prefill chunks) run by this engine (ti_engine_counters)."""

@@ -78,6 +78,44 @@ int share_prefix_option(const ModelMetadata& md, int kv_bits) {
   return n;
 }
 
+// "turboinfer.repetition_penalty" / TI_REPETITION_PENALTY (default 1), "turboinfer.presence_penalty" /
+// TI_PRESENCE_PENALTY and "turboinfer.frequency_penalty" / TI_FREQUENCY_PENALTY (default 0): the penalties of
+// ti_engine_set_penalties over each request's whole context (the reference's GenerationConfig has no such fields).
+// Parsed as floats; anything else, a repetition that is not finite and > 0 or a non-finite presence / frequency
+// throws.  Active (values other than 1, 0, 0): generate / generate_batch always take the sampled device loop (a
+// greedy config runs top_k = 1), the host-sampler loop applies ti_penalize_logits, beam search throws.
+float float_option(const ModelMetadata& md, const char* key, const char* env, float dflt) {
+  const char* v = nullptr;
+  const auto it = md.extra_params.find(key);
+  if (it != md.extra_params.end()) v = it->second.c_str();
+  else v = std::getenv(env);
+  if (!v) return dflt;
+  char* end = nullptr;
+  const float f = std::strtof(v, &end);
+  while (end && (*end == ' ' || *end == '\t')) ++end;
+  if (end == v || *end != '\0' || !std::isfinite(f))
+    throw std::runtime_error(std::string("InferenceEngine: ") + key + " must be a finite number, not \"" + v + "\"");
+  return f;
+}
+
+struct Penalties {
+  float repetition = 1.0f, presence = 0.0f, frequency = 0.0f;
+  bool active() const { return repetition != 1.0f || presence != 0.0f || frequency != 0.0f; }
+};
+
+Penalties penalty_options(const ModelMetadata& md, int lookahead, bool compat) {
+  Penalties p;
+  p.repetition = float_option(md, "turboinfer.repetition_penalty", "TI_REPETITION_PENALTY", 1.0f);
+  p.presence = float_option(md, "turboinfer.presence_penalty", "TI_PRESENCE_PENALTY", 0.0f);
+  p.frequency = float_option(md, "turboinfer.frequency_penalty", "TI_FREQUENCY_PENALTY", 0.0f);
+  if (!(p.repetition > 0.0f)) throw std::runtime_error("InferenceEngine: repetition_penalty must be greater than 0");
+  if (p.active() && lookahead > 0)
+    throw std::runtime_error("InferenceEngine: penalties and lookahead exclude each other (the verify rows are not penalised)");
+  if (p.active() && compat)
+    throw std::runtime_error("InferenceEngine: penalties need the device engine, not the reference_compat plumbing model");
+  return p;
+}
+
 [[noreturn]] void off_path(const std::string& what, const char* row) {
   throw std::runtime_error("InferenceEngine::" + what + ": not part of the MI355X decode hot path (SURVEY.md 8(f) " +
                            row + ")");
@@ -273,6 +311,7 @@ class InferenceEngineImpl {
   int kv_bits = 16;      // 8: e4m3 KV cache (TI_BITS_KV8 at ti_engine_create; cfg.bits stays the weight format)
   int lookahead = 0;     // > 0: a request that runs alone (greedy or sampled) verifies this many n-gram drafts per step
   int share_prefix = 0;  // > 0: a device-loop group whose prompts share at least this many leading tokens registers them
+  Penalties pen;         // active: every request runs the sampled device loop under ti_engine_set_penalties
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -376,6 +415,7 @@ class InferenceEngineImpl {
     check(ti_engine_create(&ec, &eng), "ti_engine_create");
     // generate() ends its device loop at EOS (token id 2, inference_engine.cpp:759-764)
     if (!compat) check(ti_engine_set_stop(eng, kGenerateEos), "ti_engine_set_stop");
+    if (pen.active()) check(ti_engine_set_penalties(eng, pen.repetition, pen.presence, pen.frequency), "ti_engine_set_penalties");
   }
 
   // Metadata without tensors (the reference's own test programs build engines this way and run
@@ -398,6 +438,7 @@ class InferenceEngineImpl {
     kv_bits = kv_bits_option(md);
     lookahead = lookahead_option(md, kv_bits);
     share_prefix = share_prefix_option(md, kv_bits);
+    pen = penalty_options(md, lookahead, false);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = 0;
     cfg.device = gpu;
@@ -473,6 +514,7 @@ class InferenceEngineImpl {
     kv_bits = kv_bits_option(md);
     lookahead = compat ? 0 : lookahead_option(md, kv_bits);
     share_prefix = compat ? 0 : share_prefix_option(md, kv_bits);
+    pen = penalty_options(md, lookahead, compat);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = compat ? 1 : 0;
     cfg.device = gpu;
@@ -648,7 +690,8 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
     return results;
   }
 
-  const bool greedy = config_.top_k == 1 && !include_logprobs;
+  // (active penalties: only the sampled device loop applies them, so a greedy config runs it with top_k = 1)
+  const bool greedy = config_.top_k == 1 && !include_logprobs && !im.pen.active();
   // The shared-prefix option: the leading tokens common to a device-loop group of two or more requests, when
   // there are at least `share_prefix` of them, are registered (prefilled once, for every stream slot, so the next
   // generate_batch with the same prefix finds them registered) and the group passes its continuations with
@@ -810,6 +853,7 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
       std::vector<int32_t> tok(n), pos(n, 0);
       std::vector<size_t> fed(n, 0);   // prompt tokens consumed
       std::vector<bool> done(n, false);
+      std::vector<int32_t> ctx;   // (active penalties: the request's prompt and new tokens so far)
       const size_t steps = stride + want - 1;
       for (size_t s = 0; s < steps; ++s) {
         for (int m = 0; m < n; ++m) {
@@ -826,6 +870,13 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
           if (fed[m] < p.size() || done[m]) {
             all_done = all_done && done[m];
             continue;
+          }
+          if (im.pen.active()) {   // the device loops' penalties, bit for bit, before the host sampler
+            ctx.assign(p.begin(), p.end());
+            ctx.insert(ctx.end(), fresh[m].begin(), fresh[m].end());
+            check(ti_penalize_logits(&logits[(size_t)m * V], V, ctx.data(), (int)ctx.size(), im.pen.repetition,
+                                     im.pen.presence, im.pen.frequency),
+                  "ti_penalize_logits");
           }
           const int t = im.sample(&logits[(size_t)m * V], config_, include_logprobs ? &lps[m] : nullptr);
           fresh[m].push_back(t);
@@ -856,6 +907,9 @@ std::vector<GenerationResult> InferenceEngine::generate_beam_search(const std::v
   validate_input_tokens(input_tokens);
   InferenceEngineImpl& im = *impl_;
   if (im.compat) off_path("generate_beam_search on the reference_compat plumbing model", "rank 4");
+  if (im.pen.active())
+    throw std::runtime_error("InferenceEngine::generate_beam_search: beam search does not apply the repetition / presence / "
+                             "frequency penalties this engine was built with");
   std::vector<GenerationResult> results;
   const int nb = (int)beam_size, mn = (int)max_new_tokens;
   std::vector<int32_t> prompt(input_tokens.begin(), input_tokens.end()), out((size_t)nb * mn);

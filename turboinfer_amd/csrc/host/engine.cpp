@@ -156,6 +156,16 @@ struct ti_engine {
   bool share_use = false;
   int share_min = 0;             // TI_SHARE_MIN: the shortest prefix that takes the shared attention
   float* share_ws = nullptr;     // ti_attn_decode_shared workspace (max_batch streams, 32 splits)
+  // ti_engine_set_penalties: active iff the values differ from (1, 0, 0).  The sampled step graphs then run
+  // ti_penalty_step between the lm_head and the sampler; the values, the state and the carry row are baked in
+  // (a change of values drops the graphs; pen_carry_on, the serve loop's, is a graph key bit).  Allocated by the
+  // first activation, outside ti_engine_memory.
+  float pen_rep = 1.0f, pen_pres = 0.0f, pen_freq = 0.0f;
+  bool pen_active() const { return pen_rep != 1.0f || pen_pres != 0.0f || pen_freq != 0.0f; }
+  ti_penalty_state pen{};        // counts / seen [max_batch][vocab], n_seen [max_batch]
+  int32_t* pen_ctx = nullptr;    // [max_seq] one stream's context on its way to ti_penalty_reset
+  int32_t* pen_carry = nullptr;  // [max_batch] each slot's input token of a serve chunk when it is a generated one
+  bool pen_carry_on = false;
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -181,7 +191,7 @@ struct ti_engine {
   }
   uint16_t** kv_tab = nullptr;   // device [2 * layers]: every layer's K then V cache base (ti_kv_copy_slots)
   size_t weight_bytes = 0, kv_bytes = 0;
-  std::map<std::pair<int, int>, hipGraphExec_t> graphs;  // (M, advance | sampled << 1 | shared prefix << 2)
+  std::map<std::pair<int, int>, hipGraphExec_t> graphs;  // (M, advance | sampled << 1 | shared prefix << 2 | carry << 3)
   int replay_M = 0;
 
   int qd() const { return c.heads * c.head_dim; }
@@ -657,6 +667,25 @@ int enqueue_step(ti_engine* e, int M, int advance) {
   stamp_tag(TI_STAMP_TAG_LM_HEAD);
   TI_TRY(gemm(e->lm, e->h, TI_X_F32_RMSNORM, H, 4, e->out_norm, el, 4, true));
   stamp_tag(TI_STAMP_TAG_OTHER);
+  if (e->samp_on && e->pen_active()) {   // the stream's context penalises the row the sampler is about to read
+    ti_penalty_args pa{};
+    pa.logits = e->logits;
+    pa.ldl = V;
+    pa.M = M;
+    pa.V = V;
+    pa.state = e->pen;
+    pa.repetition = e->pen_rep;
+    pa.presence = e->pen_pres;
+    pa.frequency = e->pen_freq;
+    pa.draw_stride = e->draw_cap;
+    pa.advance = advance;
+    pa.step_ctr = e->step_ctr;
+    pa.n_in = e->n_in;
+    pa.out_tokens = e->out_tokens;
+    pa.out_stride = e->out_cap;
+    pa.carry = e->pen_carry_on ? e->pen_carry : nullptr;
+    TI_TRY(ti_penalty_step(&pa, e->s));
+  }
   if (e->samp_on)   // sample_next_token on the device; its key feeds the token back (ti_hip.h)
     TI_TRY(ti_sample_step_ws(e->logits, V, M, V, e->samp_t, e->samp_k, e->samp_p, e->draws, e->draw_cap, e->step_ctr,
                              advance, e->n_in, e->argmax, e->lps, e->samp_ws, e->s));
@@ -797,7 +826,7 @@ int enqueue_prefill_layers(ti_engine* e, int m, int rows, int split_attn) {
 }
 
 int get_graph(ti_engine* e, int M, int advance, hipGraphExec_t* out) {
-  auto key = std::make_pair(M, advance | (e->samp_on ? 2 : 0) | (e->share_use ? 4 : 0));
+  auto key = std::make_pair(M, advance | (e->samp_on ? 2 : 0) | (e->share_use ? 4 : 0) | (e->pen_carry_on ? 8 : 0));
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) {
     *out = it->second;
@@ -853,6 +882,34 @@ int read_argmax(ti_engine* e, int n, std::vector<unsigned long long>& keys) {
     for (int j = 0; j < TI_ARGMAX_SLOTS; ++j) keys[m] = std::max(keys[m], slots[(size_t)m * TI_ARGMAX_SLOTS + j]);
   return TI_OK;
 }
+
+// Penalties (ti_engine_set_penalties).  Slot m's state becomes the histogram of head[0 .. n_head) ++
+// tail[0 .. n_tail): the registered prefix, when the stream continues it, and the prompt.
+int pen_reset_slot(ti_engine* e, int m, const int32_t* head, int n_head, const int32_t* tail, int n_tail) {
+  const int n = n_head + n_tail;
+  if (n > e->c.max_seq) return ti_set_error(TI_ERR_ARG, "engine: a penalty context of %d tokens exceeds max_seq %d", n, e->c.max_seq);
+  std::vector<int32_t> ctx((size_t)n);
+  if (n_head) std::memcpy(ctx.data(), head, (size_t)n_head * 4);
+  if (n_tail) std::memcpy(ctx.data() + n_head, tail, (size_t)n_tail * 4);
+  TI_TRY(ti_memcpy_h2d(e->pen_ctx, ctx.data(), (size_t)n * 4, e->s));
+  return ti_penalty_reset(&e->pen, e->c.vocab, m, e->pen_ctx, n, e->s);
+}
+
+// The entry points that produce tokens without the sampled step graph cannot penalise.
+int pen_refuse(const ti_engine* e, const char* fn) {
+  if (!e->pen_active()) return TI_OK;
+  return ti_set_error(TI_ERR_UNSUPPORTED, "%s: penalties are active (ti_engine_set_penalties); only ti_engine_generate_sampled "
+                      "and ti_engine_serve_sampled apply them", fn);
+}
+
+struct CarryScope {   // pen_carry_on for the duration of the serve loop's chunks
+  ti_engine* e;
+  CarryScope(ti_engine* e_, bool on) : e(e_) { e->pen_carry_on = on; }
+  ~CarryScope() { e->pen_carry_on = false; }
+};
+
+int generate_impl(ti_engine* e, int n, const int32_t* prompts, const int32_t* lens, int stride, const int32_t* start_pos,
+                  int max_new, int32_t* out_tokens, float* last_logits);
 
 }  // namespace
 
@@ -1147,6 +1204,17 @@ int ti_engine_read_kv(ti_engine* e, int layer, int stream, int which, int pos0, 
 int ti_engine_generate(ti_engine* e, int n, const int32_t* prompts, const int32_t* lens, int stride,
                        const int32_t* start_pos, int max_new, int32_t* out_tokens, float* last_logits) {
   if (!e || !prompts || !lens || !out_tokens) return ti_set_error(TI_ERR_ARG, "ti_engine_generate: null");
+  TI_TRY(pen_refuse(e, "ti_engine_generate"));
+  return generate_impl(e, n, prompts, lens, stride, start_pos, max_new, out_tokens, last_logits);
+}
+
+}  // extern "C"
+
+namespace {
+// ti_engine_generate's body, shared with ti_engine_generate_sampled (samp_on set around the call)
+int generate_impl(ti_engine* e, int n, const int32_t* prompts, const int32_t* lens, int stride, const int32_t* start_pos,
+                  int max_new, int32_t* out_tokens, float* last_logits) {
+  if (!e || !prompts || !lens || !out_tokens) return ti_set_error(TI_ERR_ARG, "ti_engine_generate: null");
   DeviceScope bind_(e);
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_generate: use ti_engine_compat_step for compat engines");
@@ -1173,6 +1241,11 @@ int ti_engine_generate(ti_engine* e, int n, const int32_t* prompts, const int32_
   TI_TRY(ti_memcpy_h2d(e->in_tokens, in.data(), in.size() * 4, e->s));
   TI_TRY(ti_memcpy_h2d(e->n_in, nin.data(), (size_t)n * 4, e->s));
   TI_TRY(ti_memcpy_h2d(e->base_pos, base.data(), (size_t)n * 4, e->s));
+  if (e->samp_on && e->pen_active())   // each stream's context so far: the registered prefix it continues, its prompt
+    for (int m = 0; m < n; ++m) {
+      const bool head = e->share_len > 0 && m < e->share_n && base[m] == e->share_len;
+      TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), head ? e->share_len : 0, prompts + (size_t)m * stride, lens[m]));
+    }
   // All but the last prompt token of the shortest prompt go through prefill; the decode loop
   // then starts at that step (same positions, same token feed, same outputs).  Greedy streams
   // whose prompts have one length: the last prompt token is a prefill row too, and the final
@@ -1263,6 +1336,9 @@ int ti_engine_generate(ti_engine* e, int n, const int32_t* prompts, const int32_
   if (n == 1) TI_TRY(qa_fault_check(e));
   return TI_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int ti_engine_generate_sampled(ti_engine* e, int n, const int32_t* prompts, const int32_t* lens, int stride,
                                const int32_t* start_pos, int max_new, float temperature, int top_k, float top_p,
@@ -1306,7 +1382,7 @@ int ti_engine_generate_sampled(ti_engine* e, int n, const int32_t* prompts, cons
   for (int m = 0; m < n; ++m) std::memcpy(&d[(size_t)m * e->draw_cap], draws + (size_t)m * max_new, (size_t)max_new * 4);
   TI_TRY(ti_memcpy_h2d(e->draws, d.data(), d.size() * 4, e->s));
   e->samp_on = true;
-  const int rc = ti_engine_generate(e, n, prompts, lens, stride, start_pos, max_new, out_tokens, nullptr);
+  const int rc = generate_impl(e, n, prompts, lens, stride, start_pos, max_new, out_tokens, nullptr);
   e->samp_on = false;
   TI_TRY(rc);
   if (out_logprobs) {
@@ -1413,6 +1489,7 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int len, int max_
   if (beam_size < 1) return ti_set_error(TI_ERR_ARG, "ti_engine_beam_search: Beam size must be greater than 0");
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_beam_search: compat engine");
+  TI_TRY(pen_refuse(e, "ti_engine_beam_search"));
   if (len + max_new - 1 > c.max_seq)
     return ti_set_error(TI_ERR_ARG, "ti_engine_beam_search: %d + %d tokens exceed max_seq %d", len, max_new, c.max_seq);
   TI_TRY(share_clear(e));   // (the beams' slots are rewritten from row 0)
@@ -1571,6 +1648,9 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
     max_len = std::max(max_len, L);
   }
   const ShareScope share_(e, P > 0 && B >= 2 && P >= e->share_min);
+  const bool pen = sp && e->pen_active();   // (the greedy loop is refused while they are active)
+  const CarryScope carry_(e, pen);
+  std::vector<int32_t> carry(B, -1);
   TI_TRY(ensure_io(e, max_len, chunk + 1));
   for (int i = 0; i < n_req * max_new; ++i) out_tokens[i] = -1;
   for (int r = 0; r < n_req; ++r) out_len[r] = 0;
@@ -1606,7 +1686,14 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
       for (int m : fresh) {
         const int L = offsets[slot_req[m] + 1] - offsets[slot_req[m]];
         for (int t0 = 0; t0 < L - 1; t0 += pf) TI_TRY(enqueue_prefill(e, m, t0, std::min(pf, L - 1 - t0), P));
+        // the slot's histogram starts over: the registered prefix, then the whole prompt (its last token too)
+        if (pen) TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), P, prompts + offsets[slot_req[m]], L));
       }
+    }
+    if (pen) {   // a continuing slot feeds a generated token the histogram has not counted yet
+      for (int m = 0; m < B; ++m) carry[m] = slot_req[m] >= 0 ? slot_tok[m] : -1;
+      for (int m : fresh) carry[m] = -1;
+      TI_TRY(ti_memcpy_h2d(e->pen_carry, carry.data(), (size_t)B * 4, e->s));
     }
     // one chunk: every slot feeds one token at its position; no slot may run past max_seq
     int S = chunk;
@@ -1663,6 +1750,7 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
     return ti_set_error(TI_ERR_ARG, "ti_engine_serve: bad arguments");
   DeviceScope bind_(e);
   if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_serve: compat engine");
+  TI_TRY(pen_refuse(e, "ti_engine_serve"));
   return serve_loop("ti_engine_serve", e, n_req, prompts, offsets, max_new, eos, chunk, nullptr, out_tokens, out_len);
 }
 
@@ -1880,6 +1968,7 @@ int la_generate(const char* fn, ti_engine* e, int stream, const int32_t* prompt,
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
   if (e->kv8) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: TI_BITS_KV8 engine (no e4m3 key-split prefill attention)", fn);
+  TI_TRY(pen_refuse(e, fn));
   if (stream < 0 || stream >= c.max_batch) return ti_set_error(TI_ERR_ARG, "%s: stream %d of %d", fn, stream, c.max_batch);
   if (prompt_len < 1 || max_new < 1 || corpus_len < 0)
     return ti_set_error(TI_ERR_ARG, "%s: prompt_len %d max_new %d corpus_len %d", fn, prompt_len, max_new, corpus_len);
@@ -2055,6 +2144,40 @@ int ti_engine_shared_prefix(ti_engine* e, int* len, int* n_streams) {
 int ti_engine_set_stop(ti_engine* e, int32_t token) {
   if (!e || token < -1 || token >= e->c.vocab) return ti_set_error(TI_ERR_ARG, "ti_engine_set_stop: token %d", token);
   e->stop_token = token;
+  return TI_OK;
+}
+
+int ti_engine_set_penalties(ti_engine* e, float repetition, float presence, float frequency) {
+  const char* fn = "ti_engine_set_penalties";
+  if (!e) return ti_set_error(TI_ERR_ARG, "%s: null", fn);
+  if (!(std::isfinite(repetition) && repetition > 0.0f) || !std::isfinite(presence) || !std::isfinite(frequency))
+    return ti_set_error(TI_ERR_ARG, "%s: repetition %g (finite, > 0), presence %g, frequency %g (finite)", fn,
+                        (double)repetition, (double)presence, (double)frequency);
+  if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
+  if (repetition == e->pen_rep && presence == e->pen_pres && frequency == e->pen_freq) return TI_OK;
+  DeviceScope bind_(e);
+  TI_TRY(ti_stream_sync(e->s));   // the step graphs bake the values in
+  drop_graphs(e);
+  const bool on = repetition != 1.0f || presence != 0.0f || frequency != 0.0f;
+  if (on && !e->pen.counts) {
+    const ti_engine_config& c = e->c;
+    TI_TRY(e->alloc_t(&e->pen.counts, (size_t)c.max_batch * c.vocab));
+    TI_TRY(e->alloc_t(&e->pen.seen, (size_t)c.max_batch * c.vocab));
+    TI_TRY(e->alloc_t(&e->pen.n_seen, (size_t)c.max_batch));
+    TI_TRY(e->alloc_t(&e->pen_ctx, (size_t)c.max_seq));
+    TI_TRY(e->alloc_t(&e->pen_carry, (size_t)c.max_batch));
+  }
+  e->pen_rep = repetition;
+  e->pen_pres = presence;
+  e->pen_freq = frequency;
+  return TI_OK;
+}
+
+int ti_engine_get_penalties(ti_engine* e, float* repetition, float* presence, float* frequency) {
+  if (!e) return ti_set_error(TI_ERR_ARG, "ti_engine_get_penalties: null");
+  if (repetition) *repetition = e->pen_rep;
+  if (presence) *presence = e->pen_pres;
+  if (frequency) *frequency = e->pen_freq;
   return TI_OK;
 }
 

@@ -86,3 +86,31 @@ extern "C" int ti_sample_token(const float* logits_in, int V, float temperature,
   if (logprob) *logprob = std::log(p[n - 1]);
   return TI_OK;
 }
+
+// The device loops' penalties (kernels/penalty.hip) on the host: llama.cpp's llama_sampler_penalties_apply over
+// the whole context, four fp32 roundings per counted token.  This file compiles with -ffp-contract=off
+// (Makefile), so no step is folded into an fma: bit for bit the device's numbers.
+extern "C" int ti_penalize_logits(float* logits, int V, const int32_t* context, int n, float repetition, float presence,
+                                  float frequency) {
+  if (!logits || V < 1 || n < 0 || (!context && n > 0))
+    return ti_set_error(TI_ERR_ARG, "ti_penalize_logits: bad arguments (vocab %d, n %d)", V, n);
+  if (!(std::isfinite(repetition) && repetition > 0.0f) || !std::isfinite(presence) || !std::isfinite(frequency))
+    return ti_set_error(TI_ERR_ARG, "ti_penalize_logits: repetition %g (finite, > 0), presence %g, frequency %g (finite)",
+                        (double)repetition, (double)presence, (double)frequency);
+  if (repetition == 1.0f && presence == 0.0f && frequency == 0.0f) return TI_OK;   // off, not the identity
+  std::vector<int32_t> count((size_t)V, 0);
+  std::vector<int32_t> seen;
+  for (int i = 0; i < n; ++i) {
+    const int32_t v = context[i];
+    if (v < 0 || v >= V) continue;
+    if (count[(size_t)v]++ == 0) seen.push_back(v);
+  }
+  for (const int32_t v : seen) {
+    const float l = logits[v];
+    const float a = l <= 0.0f ? l * repetition : l / repetition;
+    const float b = (float)count[(size_t)v] * frequency;
+    const float d = b + presence;
+    logits[v] = a - d;
+  }
+  return TI_OK;
+}
