@@ -164,6 +164,56 @@ int ti_engine_set_penalties(ti_engine* e, float repetition, float presence, floa
 /* The values in force ((1, 0, 0) when never set); any pointer may be null. */
 int ti_engine_get_penalties(ti_engine* e, float* repetition, float* presence, float* frequency);
 
+/* Token-automaton guided decoding in the sampled device loops (no reference counterpart).  The
+ * engine has no tokenizer, so a constraint -- JSON or regex shaped text, a choice set, banned tokens, a forced
+ * continuation -- arrives as constrained-decoding toolkits precompute it: a deterministic automaton over token
+ * ids, state -> {token id -> next state}, as CSR on the host:
+ *   n_states >= 1, start in [0, n_states)
+ *   row_ptr [n_states + 1]  row_ptr[0] = 0, non-decreasing; nnz = row_ptr[n_states]
+ *   tokens  [nnz]           strictly ascending within a state, each in [0, vocab)
+ *   next    [nnz]           each in [0, n_states)
+ * and every state has at least one transition (a state that allows nothing would hand the sampler a row
+ * without a finite entry).  ti_guide_check validates exactly this (TI_ERR_ARG naming the first violation).
+ * Per stream slot the engine keeps one int32 state, -1 = free or dead: the row is left alone.  For the row that
+ * produces a stream's new token t (the sampler's own index), with 0 <= t < the draw capacity:
+ *   1. the token this step fed is consumed when it is a generated one (for t >= 1 the stream's token t - 1; for
+ *      t == 0 the serve loop's carry token): state <- next of that token in the state, or -1 when the state has
+ *      no such transition (after a stop token in a lock-step batch; the sampler's u <= 0 and last-token
+ *      fall-backs);
+ *   2. with state >= 0, every column v < vocab that is not a transition of the state becomes -inf (bits
+ *      0xFF800000); every allowed column keeps its bits.
+ * The prompt is not run through the automaton: a request starts in `start`.  Order in the step: lm_head,
+ * ti_penalty_step (when penalties are active), ti_guide_step, the sampler; reported log-probabilities are
+ * those of the constrained distribution.  top_k = 1 is constrained greedy decoding; a one-state automaton that
+ * omits some ids is a token ban; a chain of one-transition states forces a continuation. */
+typedef struct ti_guide {
+  int32_t n_states;
+  int32_t start;
+  const int64_t* row_ptr;
+  const int32_t* tokens;
+  const int32_t* next;
+} ti_guide;
+/* Engine state, like ti_engine_set_penalties: the guide is copied to the device with a per-state allow-bitmask
+ * (buffers outside what ti_engine_memory reports, replaced by the next call), every slot's state becomes -1 and
+ * the captured graphs are dropped.  A null g clears the guide; with none set the engine enqueues exactly what
+ * it does without this call.  While a guide is set:
+ *   ti_engine_generate_sampled puts every stream in `start` before its first step and runs ti_guide_step in
+ *     its step graph (shared prefix included).
+ *   ti_engine_serve_sampled puts a slot in `start` when a request is admitted into it, and passes each
+ *     chunk's input token in the carry row, whatever slot and chunk a request runs in.
+ *   ti_engine_generate, ti_engine_serve, both lookahead calls and ti_engine_beam_search produce tokens and
+ *     cannot follow a guide: TI_ERR_UNSUPPORTED, naming the function, before anything is enqueued.
+ *   ti_engine_step, ti_engine_score, the replay / timing entry points return the model's own numbers.
+ * One automaton per engine; a union automaton is the caller's way to several.  Any KV format.
+ * TI_ERR_ARG: null e, a guide ti_guide_check rejects for the engine's vocab.  TI_ERR_UNSUPPORTED: a compat engine. */
+int ti_engine_set_guide(ti_engine* e, const ti_guide* g);
+/* out [max_batch]: every slot's current state (-1 everywhere when no guide is set).  After a sampled call a
+ * slot holds the state its last step masked with: every generated token but the last consumed (a step consumes
+ * the token it is fed); a caller that continues a request advances it by that last token (ti_guide_apply).  In a
+ * lock-step batch of unequal prompt lengths, or behind a stop token, a stream steps on to the batch's last step
+ * and its state follows the tokens of those steps, which the call does not return. */
+int ti_engine_guide_states(ti_engine* e, int32_t* out);
+
 /* InferenceEngine::generate_beam_search (inference_engine.cpp:830-871, 1912-2069): the
  * reference's beam loop (max-heap on log-probability, expansion by the beam_size most probable
  * tokens after temperature / softmax / top-k / top-p renormalisation (:1798-1910), length-
@@ -377,6 +427,16 @@ int ti_sample_token(const float* logits, int vocab, float temperature, int top_k
  * null context with n > 0, repetition not finite and > 0, presence or frequency not finite. */
 int ti_penalize_logits(float* logits, int vocab, const int32_t* context, int n, float repetition, float presence,
                        float frequency);
+/* The guide of ti_engine_set_guide on the host, bit for bit what the device writes (ti_hip.h ti_guide_step),
+ * for callers' own loops over ti_engine_step + ti_sample_token.  ti_guide_check validates g for a vocabulary
+ * (the contract above): TI_OK, or TI_ERR_ARG naming the first violation.  ti_guide_apply takes a slot's state
+ * (-1: free or dead), first consumes fed_token (-1: none; a token the state has no transition on leads to -1),
+ * stores the new state in *out_state (nullable), and with a new state >= 0 sets every logits[v], v < vocab, that
+ * is not a transition of it to -inf; all other elements, and every element under a state of -1, keep their
+ * bits.  logits may be null (advance only).  g is taken as checked.  TI_ERR_ARG: null g, vocab < 1, state
+ * outside [-1, n_states), fed_token < -1. */
+int ti_guide_check(const ti_guide* g, int vocab);
+int ti_guide_apply(const ti_guide* g, int vocab, int state, int fed_token, float* logits, int* out_state);
 
 #ifdef __cplusplus
 }

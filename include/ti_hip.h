@@ -631,6 +631,52 @@ typedef struct ti_penalty_args {
 } ti_penalty_args;
 int ti_penalty_step(const ti_penalty_args* a, ti_stream_t s);
 
+/* ------------------------------------------------------- token-automaton guided decoding
+ * A guide is a deterministic automaton over token ids, state -> {token id -> next state} (ti_engine.h ti_guide
+ * states the contract).  On the device it is its CSR -- row_ptr [n_states + 1] int64, tokens [nnz] strictly
+ * ascending within a state, next [nnz] -- and one allow-bitmask per state, mask [n_states][mask_words],
+ * mask_words = ceil(V / 32), bit (v & 31) of word (v >> 5) set iff the state has a transition on v (bits at or
+ * above V clear).  The caller builds both on the host and owns the memory; the kernel only reads them.
+ * state [M] int32: each stream slot's current state, -1 = free (its row is left alone).
+ * ti_guide_reset sets state[first .. first + count) to value (-1 or a state) on the stream: admission, not
+ * meant for graph capture.  TI_ERR_ARG (nothing enqueued): null state, first < 0, count < 1, value < -1. */
+typedef struct ti_guide_dev {
+  int32_t n_states;
+  int32_t mask_words;          /* ceil(V / 32) */
+  const int64_t* row_ptr;
+  const int32_t* tokens;
+  const int32_t* next;
+  const uint32_t* mask;
+} ti_guide_dev;
+int ti_guide_reset(int32_t* state, int first, int count, int32_t value, ti_stream_t s);
+/* The decode loop's form (graph-capturable; behind ti_penalty_step when that runs, before ti_sample_step; one
+ * workgroup per stream).  Stream m's draw index is ti_sample_step's: t = (*step_ctr - advance) - (n_in[m] - 1),
+ * t = 0 with a null step_ctr (n_in null: 1).  With t < 0 or t >= draw_stride nothing happens.  Otherwise one
+ * thread first consumes the token this step fed when it is a generated one -- ti_penalty_step's rule: for t >= 1
+ * out_tokens[m*out_stride + t - 1], for t == 0 carry[m] when carry is non-null and carry[m] >= 0 -- by a binary
+ * search in the state's token list: state[m] becomes that transition's next state, or -1 (dead) when the state
+ * has none.  A state outside [0, n_states) counts as -1.  Then, with state[m] >= 0, the workgroup streams the
+ * row once: every column v < V whose mask bit is clear becomes -inf (bits 0xFF800000); allowed columns and
+ * columns >= V keep their bits (16-byte stores where the row's address allows, scalar ones at its edges).
+ * Nothing but the stream's own row and state word is written.
+ * TI_ERR_ARG (nothing launched): null args / logits / state / row_ptr / tokens / next / mask, null out_tokens
+ * with a step_ctr, M < 1, V < 1, ldl < V, n_states < 1, mask_words != ceil(V / 32), draw_stride < 1,
+ * out_stride < 0. */
+typedef struct ti_guide_args {
+  float* logits;               /* [M][ldl] */
+  int32_t ldl, M, V;
+  ti_guide_dev guide;
+  int32_t* state;              /* [M] */
+  int32_t draw_stride;
+  int32_t advance;
+  const int32_t* step_ctr;     /* nullable: t = 0 */
+  const int32_t* n_in;         /* [M], nullable: 1 */
+  const int32_t* out_tokens;   /* [M][out_stride], ti_step_args' feed record */
+  int32_t out_stride;
+  const int32_t* carry;        /* [M], nullable */
+} ti_guide_args;
+int ti_guide_step(const ti_guide_args* a, ti_stream_t s);
+
 /* -------------------------------------------------------------- fp32 op level */
 /* y[r][n] (+)= sum_k a[r][k]*b[k][n], b the reference [K][N] fp32 layout, one fmaf per k
  * in ascending order (bit-identical to matmul_3d_2d).  mode: 0 store, 1 relu(store),

@@ -33,6 +33,11 @@
 //     TI_PRESENCE_PENALTY, "turboinfer.frequency_penalty" / TI_FREQUENCY_PENALTY (default 0): penalties over each
 //     request's whole context (ti_engine_set_penalties); generate / generate_batch then take the
 //     sampled device loop, beam search throws; no number, a repetition <= 0, or lookahead as well: throws.
+//   * "turboinfer.guide_file" / TI_GUIDE_FILE: a token automaton for guided decoding (ti_engine_set_guide, DESIGN
+//     4.27) in a little-endian file: "TIGD", int32 version 1, int32 n_states, int32 start, int64 nnz, int64
+//     row_ptr[n_states + 1], int32 tokens[nnz], int32 next[nnz]; generate / generate_batch then take the sampled
+//     device loop (a greedy config runs top_k = 1), beam search throws; an unreadable or invalid file, or
+//     lookahead as well: throws.
 // TensorEngine binds the device TI_GPU_INDEX names (default 0).
 //
 // Model forms accepted (reference weight names, inference_engine.cpp:483-563):

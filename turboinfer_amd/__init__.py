@@ -87,6 +87,26 @@ class PenaltyArgs(C.Structure):
                 ("out_stride", C.c_int32), ("carry", C.c_void_p)]
 
 
+class Guide(C.Structure):
+    """ti_guide (include/ti_engine.h): a token automaton as CSR on the host."""
+    _fields_ = [("n_states", C.c_int32), ("start", C.c_int32), ("row_ptr", C.c_void_p), ("tokens", C.c_void_p),
+                ("next", C.c_void_p)]
+
+
+class GuideDev(C.Structure):
+    """ti_guide_dev (include/ti_hip.h): the CSR and the per-state allow-bitmask [n_states][mask_words] on the device."""
+    _fields_ = [("n_states", C.c_int32), ("mask_words", C.c_int32), ("row_ptr", C.c_void_p), ("tokens", C.c_void_p),
+                ("next", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class GuideArgs(C.Structure):
+    """ti_guide_args (include/ti_hip.h)."""
+    _fields_ = [("logits", C.c_void_p), ("ldl", C.c_int32), ("M", C.c_int32), ("V", C.c_int32),
+                ("guide", GuideDev), ("state", C.c_void_p), ("draw_stride", C.c_int32), ("advance", C.c_int32),
+                ("step_ctr", C.c_void_p), ("n_in", C.c_void_p), ("out_tokens", C.c_void_p),
+                ("out_stride", C.c_int32), ("carry", C.c_void_p)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("inter", C.c_int32),
@@ -129,6 +149,7 @@ EXPORTED = [
     "ti_lookahead_sample", "ti_engine_generate_lookahead_sampled", "ti_engine_serve_sampled",
     "ti_attn_decode_shared", "ti_attn_shared_workspace_bytes", "ti_engine_share_prefix", "ti_engine_shared_prefix",
     "ti_penalty_reset", "ti_penalty_step", "ti_penalize_logits", "ti_engine_set_penalties", "ti_engine_get_penalties",
+    "ti_guide_reset", "ti_guide_step", "ti_guide_check", "ti_guide_apply", "ti_engine_set_guide", "ti_engine_guide_states",
 ]
 
 _lib = None
@@ -277,6 +298,13 @@ def lib() -> C.CDLL:
             L.ti_penalize_logits.argtypes = [vp, i32, vp, i32, f32, f32, f32]
             L.ti_engine_set_penalties.argtypes = [vp, f32, f32, f32]
             L.ti_engine_get_penalties.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
+        if hasattr(L, "ti_guide_step"):   # (older TI_LIB builds in A/B runs lack the guides)
+            L.ti_guide_reset.argtypes = [vp, i32, i32, i32, vp]
+            L.ti_guide_step.argtypes = [C.POINTER(GuideArgs), vp]
+            L.ti_guide_check.argtypes = [C.POINTER(Guide), i32]
+            L.ti_guide_apply.argtypes = [C.POINTER(Guide), i32, i32, i32, vp, C.POINTER(C.c_int)]
+            L.ti_engine_set_guide.argtypes = [vp, C.POINTER(Guide)]
+            L.ti_engine_guide_states.argtypes = [vp, vp]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -440,6 +468,35 @@ def penalize_logits(logits, context, repetition=1.0, presence=0.0, frequency=0.0
     check(lib().ti_penalize_logits(_ptr(lg), lg.size, _ptr(ctx) if ctx.size else None, ctx.size, repetition, presence,
                                    frequency))
     return lg
+
+
+def make_guide(row_ptr, tokens, next, start=0):
+    """(Guide, keepalive): the ctypes ti_guide over int64 / int32 copies of the CSR arrays; the struct points into
+    the arrays of `keepalive`, which the caller holds for as long as it uses the struct."""
+    rp = np.ascontiguousarray(row_ptr, np.int64).reshape(-1)
+    tk = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+    nx = np.ascontiguousarray(next, np.int32).reshape(-1)
+    if rp.size < 2 or tk.size != nx.size or rp[-1] != tk.size:
+        raise ValueError(f"guide: row_ptr of {rp.size} entries ending at {rp[-1] if rp.size else None}, "
+                         f"{tk.size} tokens, {nx.size} next states")
+    g = Guide(rp.size - 1, start, _ptr(rp), _ptr(tk) if tk.size else None, _ptr(nx) if nx.size else None)
+    return g, (rp, tk, nx)
+
+
+def guide_check(row_ptr, tokens, next, start, vocab) -> None:
+    """ti_guide_check: raises TiError naming the first violation of the guide contract (include/ti_engine.h)."""
+    g, _keep = make_guide(row_ptr, tokens, next, start)
+    check(lib().ti_guide_check(C.byref(g), vocab))
+
+
+def guide_apply(guide, state, fed_token, logits):
+    """The product's host guide step (ti_guide_apply, bit for bit the device's): `guide` = (row_ptr, tokens, next)
+    -> (new state, float32 copy of `logits` [vocab] with every id the new state does not allow at -inf)."""
+    g, _keep = make_guide(*guide)
+    lg = np.array(logits, np.float32).reshape(-1)
+    s = C.c_int()
+    check(lib().ti_guide_apply(C.byref(g), lg.size, state, fed_token, _ptr(lg), C.byref(s)))
+    return s.value, lg
 
 
 def logprob_rows(logits: DeviceBuffer, ld: int, rows: int, vocab: int, targets: DeviceBuffer,
@@ -652,6 +709,23 @@ class Engine:
         context (ti_engine_set_penalties; llama.cpp's arithmetic).  (1, 0, 0) is off.  While active, generate, serve,
         the lookahead calls and beam_search raise ti error 3; step and score stay unpenalised."""
         check(lib().ti_engine_set_penalties(self.h, repetition, presence, frequency))
+
+    def set_guide(self, row_ptr, tokens=None, next=None, start=0):
+        """Token-automaton guided decoding in generate_sampled and serve_sampled (ti_engine_set_guide): the automaton
+        state -> {token id -> next state} as CSR (row_ptr int64 [n_states + 1], tokens ascending within a state,
+        next), every request starting in `start`.  set_guide(None) clears it.  While set, generate, serve, the
+        lookahead calls and beam_search raise."""
+        if row_ptr is None:
+            check(lib().ti_engine_set_guide(self.h, None))
+            return
+        g, _keep = make_guide(row_ptr, tokens, next, start)
+        check(lib().ti_engine_set_guide(self.h, C.byref(g)))
+
+    def guide_states(self) -> np.ndarray:
+        """int32 [max_batch]: every slot's automaton state, -1 = free or dead (ti_engine_guide_states)."""
+        out = np.empty(self.cfg.max_batch, np.int32)
+        check(lib().ti_engine_guide_states(self.h, _ptr(out)))
+        return out
 
     def penalties(self):
         """(repetition, presence, frequency) in force (ti_engine_get_penalties)."""

@@ -10,7 +10,9 @@
 #include <algorithm>
 #include <map>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <iomanip>
 #include <random>
@@ -114,6 +116,57 @@ Penalties penalty_options(const ModelMetadata& md, int lookahead, bool compat) {
   if (p.active() && compat)
     throw std::runtime_error("InferenceEngine: penalties need the device engine, not the reference_compat plumbing model");
   return p;
+}
+
+// "turboinfer.guide_file" / TI_GUIDE_FILE: a token automaton for guided decoding (ti_engine_set_guide)
+// in a little-endian file: magic "TIGD", int32 version 1, int32 n_states, int32 start, int64 nnz,
+// int64 row_ptr[n_states + 1], int32 tokens[nnz], int32 next[nnz].  With a guide generate / generate_batch always
+// take the sampled device loop (a greedy config runs top_k = 1), the host-sampler loop applies ti_guide_apply, beam
+// search and lookahead throw; an unreadable or malformed file throws naming the reason (the automaton itself is
+// validated by ti_engine_set_guide against the model's vocabulary).
+struct GuideFile {
+  std::vector<int64_t> row_ptr;
+  std::vector<int32_t> tokens, next;
+  int32_t n_states = 0, start = 0;
+  bool active() const { return n_states > 0; }
+  ti_guide view() const { return ti_guide{n_states, start, row_ptr.data(), tokens.data(), next.data()}; }
+};
+
+GuideFile guide_option(const ModelMetadata& md, int lookahead, bool compat) {
+  GuideFile g;
+  std::string path;
+  const auto it = md.extra_params.find("turboinfer.guide_file");
+  if (it != md.extra_params.end()) path = it->second;
+  else if (const char* v = std::getenv("TI_GUIDE_FILE")) path = v;
+  if (path.empty()) return g;
+  auto fail = [&](const std::string& why) -> void {
+    throw std::runtime_error("InferenceEngine: guide_file \"" + path + "\": " + why);
+  };
+  if (lookahead > 0) fail("a guide and lookahead exclude each other (the verify rows are not guided)");
+  if (compat) fail("a guide needs the device engine, not the reference_compat plumbing model");
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) fail("cannot be opened");
+  struct Close {
+    std::FILE* f;
+    ~Close() { std::fclose(f); }
+  } close_{f};
+  char magic[4];
+  int32_t head[3];
+  int64_t nnz = 0;
+  if (std::fread(magic, 1, 4, f) != 4 || std::memcmp(magic, "TIGD", 4) != 0) fail("no TIGD magic");
+  if (std::fread(head, 4, 3, f) != 3 || std::fread(&nnz, 8, 1, f) != 1) fail("truncated header");
+  if (head[0] != 1) fail("version " + std::to_string(head[0]) + ", expected 1");
+  if (head[1] < 1 || nnz < 1 || nnz > ((int64_t)1 << 40)) fail("n_states " + std::to_string(head[1]) + ", nnz " + std::to_string(nnz));
+  g.row_ptr.resize((size_t)head[1] + 1);
+  if (std::fread(g.row_ptr.data(), 8, g.row_ptr.size(), f) != g.row_ptr.size()) fail("truncated row_ptr");
+  if (g.row_ptr.back() != nnz) fail("row_ptr ends at " + std::to_string(g.row_ptr.back()) + ", nnz is " + std::to_string(nnz));
+  g.tokens.resize((size_t)nnz);
+  g.next.resize((size_t)nnz);
+  if (std::fread(g.tokens.data(), 4, (size_t)nnz, f) != (size_t)nnz || std::fread(g.next.data(), 4, (size_t)nnz, f) != (size_t)nnz)
+    fail("truncated tokens / next");
+  g.n_states = head[1];
+  g.start = head[2];
+  return g;
 }
 
 [[noreturn]] void off_path(const std::string& what, const char* row) {
@@ -312,6 +365,7 @@ class InferenceEngineImpl {
   int lookahead = 0;     // > 0: a request that runs alone (greedy or sampled) verifies this many n-gram drafts per step
   int share_prefix = 0;  // > 0: a device-loop group whose prompts share at least this many leading tokens registers them
   Penalties pen;         // active: every request runs the sampled device loop under ti_engine_set_penalties
+  GuideFile guide;       // active: every request runs the sampled device loop under ti_engine_set_guide
   bool compat = false;
   std::mt19937 rng;
   size_t total_generations = 0, total_tokens = 0, total_forward_passes = 0;
@@ -416,6 +470,10 @@ class InferenceEngineImpl {
     // generate() ends its device loop at EOS (token id 2, inference_engine.cpp:759-764)
     if (!compat) check(ti_engine_set_stop(eng, kGenerateEos), "ti_engine_set_stop");
     if (pen.active()) check(ti_engine_set_penalties(eng, pen.repetition, pen.presence, pen.frequency), "ti_engine_set_penalties");
+    if (guide.active()) {
+      const ti_guide g = guide.view();
+      check(ti_engine_set_guide(eng, &g), "ti_engine_set_guide");
+    }
   }
 
   // Metadata without tensors (the reference's own test programs build engines this way and run
@@ -439,6 +497,7 @@ class InferenceEngineImpl {
     lookahead = lookahead_option(md, kv_bits);
     share_prefix = share_prefix_option(md, kv_bits);
     pen = penalty_options(md, lookahead, false);
+    guide = guide_option(md, lookahead, false);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = 0;
     cfg.device = gpu;
@@ -515,6 +574,7 @@ class InferenceEngineImpl {
     lookahead = compat ? 0 : lookahead_option(md, kv_bits);
     share_prefix = compat ? 0 : share_prefix_option(md, kv_bits);
     pen = penalty_options(md, lookahead, compat);
+    guide = guide_option(md, lookahead, compat);
     cfg.max_seq = (int)std::max<size_t>(1, c.max_sequence_length);
     cfg.compat = compat ? 1 : 0;
     cfg.device = gpu;
@@ -690,8 +750,8 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
     return results;
   }
 
-  // (active penalties: only the sampled device loop applies them, so a greedy config runs it with top_k = 1)
-  const bool greedy = config_.top_k == 1 && !include_logprobs && !im.pen.active();
+  // (active penalties, a guide: only the sampled device loop applies them, so a greedy config runs it with top_k = 1)
+  const bool greedy = config_.top_k == 1 && !include_logprobs && !im.pen.active() && !im.guide.active();
   // The shared-prefix option: the leading tokens common to a device-loop group of two or more requests, when
   // there are at least `share_prefix` of them, are registered (prefilled once, for every stream slot, so the next
   // generate_batch with the same prefix finds them registered) and the group passes its continuations with
@@ -854,6 +914,8 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
       std::vector<size_t> fed(n, 0);   // prompt tokens consumed
       std::vector<bool> done(n, false);
       std::vector<int32_t> ctx;   // (active penalties: the request's prompt and new tokens so far)
+      std::vector<int> gstate(n, im.guide.start);   // (a guide: each request's automaton state)
+      const ti_guide gview = im.guide.view();
       const size_t steps = stride + want - 1;
       for (size_t s = 0; s < steps; ++s) {
         for (int m = 0; m < n; ++m) {
@@ -878,6 +940,10 @@ std::vector<GenerationResult> InferenceEngine::generate_batch(const std::vector<
                                      im.pen.presence, im.pen.frequency),
                   "ti_penalize_logits");
           }
+          if (im.guide.active())   // the device loops' guide step, bit for bit: consume the token just fed, then mask
+            check(ti_guide_apply(&gview, V, gstate[m], fresh[m].empty() ? -1 : fresh[m].back(), &logits[(size_t)m * V],
+                                 &gstate[m]),
+                  "ti_guide_apply");
           const int t = im.sample(&logits[(size_t)m * V], config_, include_logprobs ? &lps[m] : nullptr);
           fresh[m].push_back(t);
           if (t == kGenerateEos || fresh[m].size() >= budget(p.size())) done[m] = true;
@@ -910,6 +976,9 @@ std::vector<GenerationResult> InferenceEngine::generate_beam_search(const std::v
   if (im.pen.active())
     throw std::runtime_error("InferenceEngine::generate_beam_search: beam search does not apply the repetition / presence / "
                              "frequency penalties this engine was built with");
+  if (im.guide.active())
+    throw std::runtime_error("InferenceEngine::generate_beam_search: beam search does not follow the guide (guide_file) this "
+                             "engine was built with");
   std::vector<GenerationResult> results;
   const int nb = (int)beam_size, mn = (int)max_new_tokens;
   std::vector<int32_t> prompt(input_tokens.begin(), input_tokens.end()), out((size_t)nb * mn);

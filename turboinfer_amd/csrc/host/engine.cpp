@@ -481,7 +481,7 @@ int ti_engine_set_penalties(ti_engine* e, float repetition, float presence, floa
     TI_TRY(e->alloc_t(&e->pen.seen, (size_t)c.max_batch * c.vocab));
     TI_TRY(e->alloc_t(&e->pen.n_seen, (size_t)c.max_batch));
     TI_TRY(e->alloc_t(&e->pen_ctx, (size_t)c.max_seq));
-    TI_TRY(e->alloc_t(&e->pen_carry, (size_t)c.max_batch));
+    if (!e->pen_carry) TI_TRY(e->alloc_t(&e->pen_carry, (size_t)c.max_batch));   // (a guide may have made it)
   }
   e->pen_rep = repetition;
   e->pen_pres = presence;

@@ -96,6 +96,7 @@ int ti_engine_beam_search(ti_engine* e, const int32_t* prompt, int len, int max_
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_beam_search: compat engine");
   TI_TRY(pen_refuse(e, "ti_engine_beam_search"));
+  TI_TRY(guide_refuse(e, "ti_engine_beam_search"));
   if (len + max_new - 1 > c.max_seq)
     return ti_set_error(TI_ERR_ARG, "ti_engine_beam_search: %d + %d tokens exceed max_seq %d", len, max_new, c.max_seq);
   TI_TRY(share_clear(e));   // (the beams' slots are rewritten from row 0)

@@ -41,6 +41,7 @@ int generate_impl(ti_engine* e, int n, const int32_t* prompts, const int32_t* le
       const bool head = e->share_len > 0 && m < e->share_n && base[m] == e->share_len;
       TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), head ? e->share_len : 0, prompts + (size_t)m * stride, lens[m]));
     }
+  if (sampled && e->guide_active()) TI_TRY(guide_start_slots(e, 0, n));   // the prompt is not run through the automaton
   // All but the last prompt token of the shortest prompt go through prefill; the decode loop
   // then starts at that step (same positions, same token feed, same outputs).  Greedy streams
   // whose prompts have one length: the last prompt token is a prefill row too, and the final
@@ -132,6 +133,7 @@ int ti_engine_generate(ti_engine* e, int n, const int32_t* prompts, const int32_
                        const int32_t* start_pos, int max_new, int32_t* out_tokens, float* last_logits) {
   if (!e || !prompts || !lens || !out_tokens) return ti_set_error(TI_ERR_ARG, "ti_engine_generate: null");
   TI_TRY(pen_refuse(e, "ti_engine_generate"));
+  TI_TRY(guide_refuse(e, "ti_engine_generate"));
   return generate_impl(e, n, prompts, lens, stride, start_pos, max_new, false, out_tokens, last_logits);
 }
 

@@ -54,9 +54,9 @@ struct DevLayer {
 // down to run_steps / get_graph / enqueue_step, which build the cache key from the same object.
 struct StepMode {
   bool advance = false;   // the lm_head advances step_ctr (the device loop); off: a replay step
-  bool sampled = false;   // ti_penalty_step (when penalties are active) + ti_sample_step behind the lm_head
+  bool sampled = false;   // ti_penalty_step / ti_guide_step (when active) + ti_sample_step behind the lm_head
   bool shared = false;    // the registered prefix attended once for all streams (ti_attn_decode_shared)
-  bool carry = false;     // the penalty step counts each slot's pen_carry token first (the serve loop's chunks)
+  bool carry = false;     // the penalty / guide step takes each slot's pen_carry token first (the serve loop's chunks)
 };
 
 // Everything a captured graph bakes in that can differ between two live graphs.  Whatever else enqueue_step or
@@ -165,6 +165,14 @@ struct ti_engine {
   ti_penalty_state pen{};        // counts / seen [max_batch][vocab], n_seen [max_batch]
   int32_t* pen_ctx = nullptr;    // [max_seq] one stream's context on its way to ti_penalty_reset
   int32_t* pen_carry = nullptr;  // [max_batch] each slot's input token of a serve chunk when it is a generated one
+  // ti_engine_set_guide (engine_guide.cpp): active iff guide.mask is set.  The sampled step graphs then run
+  // ti_guide_step behind ti_penalty_step; the device guide, the state row and the carry row (pen_carry, shared
+  // with the penalties) are baked in, and setting or clearing a guide drops the graphs.  Outside ti_engine_memory.
+  ti_guide_dev guide{};          // CSR + per-state allow-bitmask on the device (guide_bufs)
+  int guide_start = 0;
+  int32_t* guide_state = nullptr;  // [max_batch] each slot's automaton state, -1 = free or dead
+  std::vector<void*> guide_bufs;   // the live guide's device buffers, freed when it is replaced
+  bool guide_active() const { return guide.mask != nullptr; }
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -251,6 +259,7 @@ struct ti_engine {
   ~ti_engine() {
     for (auto& g : graphs) hipGraphExecDestroy(g.second);
     for (void* p : allocs) hipFree(p);
+    for (void* p : guide_bufs) hipFree(p);
     if (s) hipStreamDestroy(s);
   }
 };
@@ -298,6 +307,11 @@ int share_clear(ti_engine* e);
 int share_begin(ti_engine* e, int M, const int32_t* base, bool* use);
 int pen_reset_slot(ti_engine* e, int m, const int32_t* head, int n_head, const int32_t* tail, int n_tail);
 int pen_refuse(const ti_engine* e, const char* fn);
+
+// ---- engine_guide.cpp: ti_engine_set_guide's state
+int guide_refuse(const ti_engine* e, const char* fn);
+int guide_start_slots(ti_engine* e, int first, int count);
+int guide_enqueue(ti_engine* e, int M, StepMode mode);
 
 // ---- engine_step.cpp: projections, attention routing, the step plan and its epilogues
 bool packed_rows(const ti_engine* e, int M);

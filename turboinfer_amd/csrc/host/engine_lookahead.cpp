@@ -81,6 +81,7 @@ int la_generate(const char* fn, ti_engine* e, int stream, const int32_t* prompt,
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
   if (e->kv8) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: TI_BITS_KV8 engine (no e4m3 key-split prefill attention)", fn);
   TI_TRY(pen_refuse(e, fn));
+  TI_TRY(guide_refuse(e, fn));
   if (stream < 0 || stream >= c.max_batch) return ti_set_error(TI_ERR_ARG, "%s: stream %d of %d", fn, stream, c.max_batch);
   if (prompt_len < 1 || max_new < 1 || corpus_len < 0)
     return ti_set_error(TI_ERR_ARG, "%s: prompt_len %d max_new %d corpus_len %d", fn, prompt_len, max_new, corpus_len);

@@ -37,7 +37,8 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
     max_len = std::max(max_len, L);
   }
   const bool pen = sp && e->pen_active();   // (the greedy loop is refused while they are active)
-  const StepMode mode{true, sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen};
+  const bool guide = sp && e->guide_active();
+  const StepMode mode{true, sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen || guide};
   std::vector<int32_t> carry(B, -1);
   TI_TRY(ensure_io(e, max_len, chunk + 1));
   for (int i = 0; i < n_req * max_new; ++i) out_tokens[i] = -1;
@@ -76,9 +77,10 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
         TI_TRY(prefill_tokens(e, m, L - 1, P));
         // the slot's histogram starts over: the registered prefix, then the whole prompt (its last token too)
         if (pen) TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), P, prompts + offsets[slot_req[m]], L));
+        if (guide) TI_TRY(guide_start_slots(e, m, 1));   // a freed slot restarts at the guide's start state
       }
     }
-    if (pen) {   // a continuing slot feeds a generated token the histogram has not counted yet
+    if (pen || guide) {   // a continuing slot feeds a generated token the histogram / the automaton has not seen yet
       for (int m = 0; m < B; ++m) carry[m] = slot_req[m] >= 0 ? slot_tok[m] : -1;
       for (int m : fresh) carry[m] = -1;
       TI_TRY(ti_memcpy_h2d(e->pen_carry, carry.data(), (size_t)B * 4, e->s));
@@ -140,6 +142,7 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
   DeviceScope bind_(e);
   if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_serve: compat engine");
   TI_TRY(pen_refuse(e, "ti_engine_serve"));
+  TI_TRY(guide_refuse(e, "ti_engine_serve"));
   return serve_loop("ti_engine_serve", e, n_req, prompts, offsets, max_new, eos, chunk, nullptr, out_tokens, out_len);
 }
 

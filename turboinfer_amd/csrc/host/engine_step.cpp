@@ -348,6 +348,8 @@ int enqueue_step(ti_engine* e, int M, StepMode mode) {
     pa.carry = mode.carry ? e->pen_carry : nullptr;
     TI_TRY(ti_penalty_step(&pa, e->s));
   }
+  if (mode.sampled && e->guide_active())   // the stream's automaton state masks the row (-inf survives the penalties)
+    TI_TRY(guide_enqueue(e, M, mode));
   if (mode.sampled)   // sample_next_token on the device; its key feeds the token back (ti_hip.h)
     TI_TRY(ti_sample_step_ws(e->logits, V, M, V, e->samp_t, e->samp_k, e->samp_p, e->draws, e->draw_cap, e->step_ctr,
                              mode.advance, e->n_in, e->argmax, e->lps, e->samp_ws, e->s));

@@ -114,3 +114,53 @@ extern "C" int ti_penalize_logits(float* logits, int V, const int32_t* context, 
   }
   return TI_OK;
 }
+
+// Guided decoding (kernels/guide.hip) on the host: the contract of ti_engine.h ti_guide, validated here ...
+extern "C" int ti_guide_check(const ti_guide* g, int V) {
+  const char* fn = "ti_guide_check";
+  if (!g || !g->row_ptr) return ti_set_error(TI_ERR_ARG, "%s: null guide or row_ptr", fn);
+  if (V < 1) return ti_set_error(TI_ERR_ARG, "%s: vocab %d", fn, V);
+  const int n = g->n_states;
+  if (n < 1) return ti_set_error(TI_ERR_ARG, "%s: n_states %d < 1", fn, n);
+  if (g->start < 0 || g->start >= n) return ti_set_error(TI_ERR_ARG, "%s: start %d outside [0, n_states %d)", fn, g->start, n);
+  if (g->row_ptr[0] != 0) return ti_set_error(TI_ERR_ARG, "%s: row_ptr[0] = %lld, not 0", fn, (long long)g->row_ptr[0]);
+  if (!g->tokens || !g->next) return ti_set_error(TI_ERR_ARG, "%s: null tokens or next", fn);
+  for (int s = 0; s < n; ++s) {   // (before any list is read: a monotone row_ptr keeps every index below nnz)
+    if (g->row_ptr[s + 1] < g->row_ptr[s]) return ti_set_error(TI_ERR_ARG, "%s: row_ptr decreases at state %d", fn, s);
+    if (g->row_ptr[s + 1] == g->row_ptr[s]) return ti_set_error(TI_ERR_ARG, "%s: state %d has no transition", fn, s);
+  }
+  for (int s = 0; s < n; ++s) {
+    const int64_t b = g->row_ptr[s], e = g->row_ptr[s + 1];
+    for (int64_t i = b; i < e; ++i) {
+      const int32_t v = g->tokens[i], nx = g->next[i];
+      if (v < 0 || v >= V) return ti_set_error(TI_ERR_ARG, "%s: state %d: token %d outside [0, vocab %d)", fn, s, v, V);
+      if (i > b && v <= g->tokens[i - 1])
+        return ti_set_error(TI_ERR_ARG, "%s: state %d: token %d after %d (strictly ascending ids)", fn, s, v, g->tokens[i - 1]);
+      if (nx < 0 || nx >= n) return ti_set_error(TI_ERR_ARG, "%s: state %d: next %d outside [0, n_states %d)", fn, s, nx, n);
+    }
+  }
+  return TI_OK;
+}
+
+// ... and applied to one host row: the advance by the fed token, then -inf at every id the state does not allow.
+extern "C" int ti_guide_apply(const ti_guide* g, int V, int state, int fed_token, float* logits, int* out_state) {
+  if (!g || !g->row_ptr || !g->tokens || !g->next || V < 1 || g->n_states < 1 || state < -1 || state >= g->n_states ||
+      fed_token < -1)
+    return ti_set_error(TI_ERR_ARG, "ti_guide_apply: bad arguments (vocab %d, state %d, fed_token %d)", V, state, fed_token);
+  int s = state;
+  if (s >= 0 && fed_token >= 0) {
+    const int32_t* b = g->tokens + g->row_ptr[s];
+    const int32_t* e = g->tokens + g->row_ptr[s + 1];
+    const int32_t* at = std::lower_bound(b, e, (int32_t)fed_token);
+    s = at != e && *at == fed_token ? g->next[at - g->tokens] : -1;
+  }
+  if (out_state) *out_state = s;
+  if (s < 0 || !logits) return TI_OK;
+  int64_t i = g->row_ptr[s];
+  const int64_t end = g->row_ptr[s + 1];
+  for (int v = 0; v < V; ++v) {
+    if (i < end && g->tokens[i] == v) ++i;
+    else logits[v] = -std::numeric_limits<float>::infinity();
+  }
+  return TI_OK;
+}

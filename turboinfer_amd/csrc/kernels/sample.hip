@@ -262,6 +262,13 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
     own([&](int, uint32_t key, bool ok) { tmax = ok && key > tmax ? key : tmax; });
     int unused;
     select_kth([&](auto&& f) { f(tmax); }, k, &tau0, &unused);
+    // A row that is mostly -inf (a guide's mask, ti_guide_step): fewer than k threads hold a finite logit, the
+    // bound is -inf's key and every column would be a candidate -- the radix select over a row of one value,
+    // 87 us instead of 29.  The keys above -inf alone are then the candidates: an entry at -inf
+    // carries probability exactly 0 whether it survives or not, so token and log p are the same with fewer
+    // than k survivors.  (tau0 is block-uniform; a row without any such key keeps the old route.)
+    constexpr uint32_t kNegInfKey = 0x00800000u;   // samp_key(-inf)
+    if (tau0 <= kNegInfKey && __syncthreads_or(tmax > kNegInfKey)) tau0 = kNegInfKey + 1u;
     int ncand = 0;
     own([&](int, uint32_t key, bool ok) { ncand += ok && key >= tau0; });
     cbase = wave_base(ncand, &tot);
