@@ -294,6 +294,12 @@ int ti_gemm_grid(int M, int N, int K);
  * rows): the fold_ss partials per row its TI_EPI_RESID_F32 fold epilogue writes (0 = the call
  * does not take the batched-rows kernel). */
 int ti_gemm_fold_partials(int bits, int M, int N, int K);
+/* The plan of the register-fragment batched kernel (gemv_mbr_kernel: int4 TI_X_F16 rows beyond the
+ * fused kernel's preference, 3..16 of them at most shapes) for an M x N x K call: *grid workgroups,
+ * each holding *ntl or *ntl - 1 of the N / 16 weight tiles (workgroup b takes tiles
+ * [b * (N / 16) / grid, (b + 1) * (N / 16) / grid)); *ntl is 1..8.  For tests that mean to run one
+ * instance of the kernel.  TI_ERR_UNSUPPORTED when the call would take another kernel. */
+int ti_gemm_mb_plan(int bits, int M, int N, int K, int* grid, int* ntl);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

@@ -1,6 +1,8 @@
-"""The batched-rows GEMM (gemv_mb_kernel: int4 x fp16 rows beyond the fused kernel's LDS
-image, generate_batch's M = B decode, inference_engine.cpp:804-828) and its rms_norm prep,
-through the ti_hip.h C-ABI, against the oracle's dequantized weights.
+"""The batched GEMMs (int4 x fp16 rows beyond the fused kernel: generate_batch's M = B decode,
+inference_engine.cpp:804-828, and prefill chunks) and their rms_norm prep, through the ti_hip.h
+C-ABI, against the oracle's dequantized weights: gemv_mbr_kernel (3..16 rows; its tile counts, K
+edges and epilogues are in test_gpu_gemv_mbr.py), gemm_rows_kernel (17..64 rows) and
+gemm_tile_kernel (wide outputs from 17 rows, everything from 65 rows).
 
 Tolerance as in test_gpu_kernels.py: the expected values use the same fp16 activations and
 the oracle's exact int4 x scale weights in float64, so what is left is fp32 summation order
@@ -46,24 +48,38 @@ def run(ti, tiles, scales, x16, M, N, K, ep, ws=None):
         assert not ws.download(np.int32, (TICKET_BYTES // 4,)).any(), "split-K tickets not re-armed"
 
 
-# (M, K, N): rows 17-32 (two 16-row blocks), long K at few rows (one block), ragged tiles per
-# workgroup (N/16 not a multiple of the grid), a last k-chunk of fewer than 8 k-tiles,
-# more tiles than 5 per workgroup (grid grows)
-@pytest.mark.parametrize("M,K,N", [(17, 1024, 64), (32, 4096, 4096 + 48), (24, 1152, 4000), (8, 11008, 256),
-                                   (3, 14336, 96), (20, 4096, 25600), (32, 384, 16), (64, 4096, 12288),
-                                   (48, 11008, 4096 + 16), (33, 1152, 4000), (64, 384, 16), (64, 14336, 256),
-                                   (40, 4096, 32000), (128, 4096, 4096), (200, 1152, 4000 + 16), (256, 11008, 512),
-                                   (129, 384, 16),
-                                   # tile kernel at prefill chunks: 128 / 64 columns per workgroup, ragged tiles and rows
-                                   (512, 4096, 22016), (700, 4096, 12288 + 48), (1000, 1152, 4000 + 16),
-                                   (1024, 384, 16),
-                                   # split K (with the workspace): narrow outputs at 65-128 rows, ragged slices
-                                   (65, 4096, 4096), (128, 11008, 4096 + 16), (100, 14336, 512), (96, 3200, 1040)])
+MBR, ROWS, TILE = "gemv_mbr_kernel", "gemm_rows_kernel", "gemm_tile_kernel"
+
+
+def shape(M, K, N, kernel):
+    return pytest.param(M, K, N, kernel, id=f"{M}-{K}-{N}")
+
+
+# (M, K, N, the kernel the call takes: gemv_mbr_kernel up to 16 rows, gemm_rows_kernel up to 64 rows
+# except wide outputs, gemm_tile_kernel for those and from 65 rows on).
+# Rows kernel: 17-32 rows (one group of two 16-row blocks) and 33-64 rows (two groups), ragged tiles
+# per workgroup (N/16 not a multiple of the column groups), k-tiles that do not fill the waves' last
+# round; 20 x 25600 and 40 x 32000 are wide outputs (the tile kernel's 32-row and 64-row waves).
+# gemv_mbr_kernel: long K at few rows, one tile per workgroup (test_gpu_gemv_mbr.py has its other plans).
+@pytest.mark.parametrize("M,K,N,kernel", [
+    shape(17, 1024, 64, ROWS), shape(32, 4096, 4096 + 48, ROWS), shape(24, 1152, 4000, ROWS),
+    shape(8, 11008, 256, MBR), shape(3, 14336, 96, MBR), shape(20, 4096, 25600, TILE), shape(32, 384, 16, ROWS),
+    shape(64, 4096, 12288, ROWS), shape(48, 11008, 4096 + 16, ROWS), shape(33, 1152, 4000, ROWS),
+    shape(64, 384, 16, ROWS), shape(64, 14336, 256, ROWS), shape(40, 4096, 32000, TILE),
+    shape(128, 4096, 4096, TILE), shape(200, 1152, 4000 + 16, TILE), shape(256, 11008, 512, TILE),
+    shape(129, 384, 16, TILE),
+    # tile kernel at prefill chunks: 128 / 64 columns per workgroup, ragged tiles and rows
+    shape(512, 4096, 22016, TILE), shape(700, 4096, 12288 + 48, TILE), shape(1000, 1152, 4000 + 16, TILE),
+    shape(1024, 384, 16, TILE),
+    # split K (with the workspace): narrow outputs at 65-128 rows, ragged slices
+    shape(65, 4096, 4096, TILE), shape(128, 11008, 4096 + 16, TILE), shape(100, 14336, 512, TILE),
+    shape(96, 3200, 1040, TILE)])
 @pytest.mark.parametrize("splitk", [False, True])
-def test_batched_store(ti, oracle, splitk_ws, M, K, N, splitk):
-    """Without a workspace: the batched-rows kernels (<= 64 rows) and the tile kernel; with one
-    (the engine's form), the tile kernel splits K over workgroups where the plan
+def test_batched_store(ti, oracle, splitk_ws, M, K, N, kernel, splitk):
+    """Without a workspace: gemv_mbr_kernel (<= 16 rows), the rows kernel (<= 64 rows) and the tile
+    kernel; with one (the engine's form), the tile kernel splits K over workgroups where the plan
     (ti_gemm_tile_plan) says so."""
+    assert ti.gemm_kernel_name(4, ti.X_F16, M, N, K) == kernel
     rng = np.random.RandomState(M * 7 + K + N)
     w = (rng.standard_normal((K, N)) * 0.03).astype(f32)
     x = rng.standard_normal((M, K)).astype(f16)

@@ -224,6 +224,20 @@ def test_engine_7b_40_streams(ti, oracle):
     _full_shape_streams(ti, oracle, CFG_7B, 2025, 40, [1, 17, 35], 4)
 
 
+def test_engine_7b_8_streams(ti, oracle):
+    """8 streams of the 7B shape: every projection on gemv_mbr_kernel (3..16 int4 rows) at its
+    production plans on 256 CUs -- QKV 3 tiles per workgroup, O 1, gate/up 5 / 6, down 1, lm_head
+    7 / 8; two streams against the oracle (stream 6's reference margin is under the 3 x TOL rule at
+    this seed: streams 1 and 7)."""
+    _full_shape_streams(ti, oracle, CFG_7B, 2025, 8, [1, 7], 4)
+
+
+def test_engine_7b_13_streams(ti, oracle):
+    """13 streams of the 7B shape: the same plans with three dead rows in the 16-row block; the
+    first, a middle and the last stream against the oracle."""
+    _full_shape_streams(ti, oracle, CFG_7B, 2025, 13, [0, 7, 12], 4)
+
+
 def test_engine_compat_plumbing_matches_reference_generate(ti, oracle, golden):
     """BASELINE config 1: the reference's own generate() on its benchmark model, exact tokens
     (fp32 bit-exact path + the reference sampler's tie order)."""
@@ -273,6 +287,14 @@ def test_engine_llama3_32_streams_8192(ti, oracle):
     """BASELINE configs[4]: 32 streams of Llama-3-8B GQA shape, each with its own 8189-slot
     cache (8192-token KV), three steps to position 8191: five streams against the oracle."""
     _full_shape_streams(ti, oracle, CFG_L3, 808, 32, [2, 8, 19, 24, 31], 3)
+
+
+def test_engine_llama3_5_streams_8192(ti, oracle):
+    """5 streams of the Llama-3-8B shape on gemv_mbr_kernel: the lm_head's 8016 tiles are more than
+    8 per workgroup on 256 CUs, so its grid grows to 1002 workgroups of 8; QKV (GQA, 6144 outputs)
+    splits 1 / 2, gate/up takes 7.  Streams 0 and 4 have reference margins under the 3 x TOL rule at
+    this seed: streams 1 and 3 against the oracle."""
+    _full_shape_streams(ti, oracle, CFG_L3, 808, 5, [1, 3], 3)
 
 
 def test_engine_batch_beyond_one_gemm_chunk(ti, oracle):

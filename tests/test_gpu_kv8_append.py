@@ -1,6 +1,7 @@
-"""The TI_EPI_QKV_ROPE_KV epilogue writing an e4m3 cache (ti_epilogue.kv_fp8 = 1) on the three kernels that
-append K / V -- the fused kernel (M = 1), the batched-rows kernel (packed int4 rows) and the tile kernel
-(int4 rows from 65 on) -- and ti_fill_kv_uniform_f8.
+"""The TI_EPI_QKV_ROPE_KV epilogue writing an e4m3 cache (ti_epilogue.kv_fp8 = 1) on the four kernels that
+append K / V -- the fused kernel (M = 1), the register-fragment batched kernel (gemv_mbr_kernel, 8 int4
+rows), the batched-rows kernel (packed int4 rows) and the tile kernel (int4 rows from 65 on) -- and
+ti_fill_kv_uniform_f8.
 
 Each case runs ti_gemm_wq_a16 twice on the same inputs, kv_fp8 0 and 1, into caches pre-filled with 0xA5:
   q is bit-identical between the two calls;
@@ -41,6 +42,7 @@ def patterned(ti, nbytes):
 
 # (label, bits, M, x kind, kernel name prefix)
 KERNELS = [("fused-int4", 4, 1, "f16", "gemv_wq_kernel"), ("fused-int8", 8, 1, "f16", "gemv_wq_kernel"),
+           ("mbr-int4", 4, 8, "f16", "gemv_mbr_kernel"),
            ("rows-int4", 4, 32, "packed", "gemm_rows_kernel"), ("tile-int4", 4, 128, "f16", "gemm_tile_kernel")]
 SHAPES = [(4, 2, 64), (2, 2, 128)]      # heads, kv_heads, head_dim
 

@@ -135,7 +135,7 @@ EXPORTED = [
     "ti_wpack_q_host", "ti_engine_set_tensor_q", "ti_sample_workspace_bytes", "ti_sample_device_ws",
     "ti_wpack_q1_host", "ti_engine_set_tensor_q1", "ti_epilogue_bytes",
     "ti_sample_step_ws", "ti_hbm_calibrate", "ti_gemm_kernel_name",
-    "ti_gemm_fold_partials", "ti_engine_set_stop", "ti_engine_counters",
+    "ti_gemm_fold_partials", "ti_gemm_mb_plan", "ti_engine_set_stop", "ti_engine_counters",
     "ti_qkv_attn_partials", "ti_qkv_attn_part_o_elems", "ti_qkv_attn_part_ml_elems", "ti_engine_set_qkv_attn",
     "ti_qkv_attn_xchg_bytes", "ti_qkv_attn_supported", "ti_qkv_attn_error_offset",
     "ti_logprob_rows", "ti_engine_score",
@@ -194,6 +194,7 @@ def lib() -> C.CDLL:
         L.ti_gemm_packed_rows.argtypes = [i32, i32]
         L.ti_gemm_packed_rows_for.argtypes = [i32, i32, i32, i32]
         L.ti_gemm_tile_plan.argtypes = [i32, i32, i32, i32, C.c_int64, vp, vp, vp]
+        L.ti_gemm_mb_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ti_rmsnorm_f16.argtypes = [vp, i32, vp, f32, vp, i32, i32, i32, vp]
         L.ti_rmsnorm_f16_packed.argtypes = [vp, i32, vp, f32, vp, i32, i32, vp]
         L.ti_attn_workspace_bytes.argtypes = [i32, i32, i32, i32]

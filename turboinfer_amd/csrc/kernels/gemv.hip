@@ -26,6 +26,7 @@
 #include <math.h>
 #include <atomic>
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.hpp"
 #include "attention_body.hpp"
@@ -2973,6 +2974,20 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
   const char* name = tile ? "gemm_tile_kernel" : rows ? "gemm_rows_kernel" : batched ? (mb_use_lds(M > 16 ? 2 : 1) ? "gemv_mb_kernel" : "gemv_mbr_kernel") : nullptr;
   if (name) snprintf(buf, (size_t)len, "%s", name);
   else snprintf(buf, (size_t)len, "gemv_wq_kernel<%d,%d>", bits, gemv_xmode(x_kind, M, K));
+  return TI_OK;
+}
+
+// The register-fragment batched kernel's plan: gemm_impl's dispatch through ti_gemm_kernel_name, and
+// the mb_grid call gemm_impl makes for it (one 16-row block).
+extern "C" int ti_gemm_mb_plan(int bits, int M, int N, int K, int* grid, int* ntl) {
+  if (!grid || !ntl) return ti_set_error(TI_ERR_ARG, "ti_gemm_mb_plan: null pointer");
+  char name[32] = "";
+  if (bits != 4 || M < 1 || M > 16 || N < 16 || (N & 15) || K < 128 || (K & 127) || K > 0xffff ||
+      ti_gemm_kernel_name(bits, TI_X_F16, M, N, K, name, (int)sizeof(name)) != TI_OK ||
+      strcmp(name, "gemv_mbr_kernel") != 0)
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_mb_plan: M=%d N=%d K=%d bits %d is not a gemv_mbr_kernel call", M,
+                        N, K, bits);
+  *grid = ti::mb_grid(1, N, K, query_cus(), ntl);
   return TI_OK;
 }
 
