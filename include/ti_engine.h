@@ -251,6 +251,45 @@ int ti_engine_serve(ti_engine* e, int n_req, const int32_t* prompts, const int32
 int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets, int max_new,
                             int eos_token, int chunk, float temperature, int top_k, float top_p, const float* draws,
                             int32_t* out_tokens, int32_t* out_len, float* out_logprobs);
+/* ti_engine_serve_sampled with every request carrying its own budget, stop token, sampler parameters and
+ * penalties, all of them through one loop and one batch (a greedy extraction next to a creative completion).
+ * The launches between the lm_head and the feedback read each stream row's values from a device table
+ * [max_batch] of ti_row_params (ti_hip.h: ti_penalty_step_rows, ti_guide_step when a guide is set -- the
+ * engine's one guide, for every request, as in ti_engine_serve_sampled -- and ti_sample_step_rows).  The step
+ * graph bakes in the table's pointer only; before a chunk that follows an admission or a departure the host
+ * copies the table in stream order, as it does the draws (idle slots hold temperature 1, top_k 1, top_p 1,
+ * penalties (1, 0, 0)).  So different parameters, within a call or between calls, drop no graph.
+ *   params [n_req]; draws, out_tokens (-1 padded), out_logprobs (nullable; 0.0 past out_len) are host
+ *   [n_req][out_stride] with out_stride >= every max_new; out_len [n_req].
+ *   A request ends at its own max_new or its own stop_token (included, as eos_token is).
+ *   ti_penalty_step_rows is in the graph only when some request of the call penalises (values other than
+ *   (1, 0, 0)); only then is the penalty state allocated (as ti_engine_set_penalties allocates it), and a slot's
+ *   histogram is reset at admission only for a request that penalises: from the registered prefix, when the loop
+ *   treats prompts as continuations of it, and the prompt.
+ *   When some request's top_k exceeds TI_SAMPLE_MAX_K the call's graph runs every row on the sampler's
+ *   workspace instance (the engine's workspace grows to max_batch rows of vocab; growing a buffer drops graphs).
+ *   ti_engine_set_penalties' values and ti_engine_set_stop do not apply to this call and are not changed by it.
+ * Contract: request r's tokens and log-probabilities are bit for bit what ti_engine_serve_sampled returns for r
+ * on an engine of the same shape and max_batch called with r's (max_new, stop_token as eos_token, temperature,
+ * top_k, top_p) and draws[r], ti_engine_set_penalties set to r's three values -- whatever the other requests'
+ * parameters, the slot and the chunking are (the batched kernels compute every row from its own inputs).
+ * Exception: in a call where some request has top_k > TI_SAMPLE_MAX_K, rows are the sampler's tokens for their own
+ * parameters (pinned to the host sampler) but not promised bit-equal to the LDS instance's.
+ * TI_ERR_ARG before anything is enqueued, naming the request: ti_engine_serve_sampled's checks, null params,
+ * max_new < 1 or > out_stride, stop_token outside [-1, vocab), top_k outside [1, vocab], penalty values
+ * ti_engine_set_penalties would reject, registered prefix + prompt + the request's max_new - 1 beyond max_seq.
+ * TI_ERR_UNSUPPORTED: a compat engine. */
+typedef struct ti_request_params {
+  int32_t max_new;                          /* >= 1 */
+  int32_t stop_token;                       /* -1: none */
+  float temperature;
+  int32_t top_k;                            /* 1 <= top_k <= vocab */
+  float top_p;
+  float repetition, presence, frequency;    /* (1, 0, 0): off */
+} ti_request_params;                        /* 32 bytes */
+int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                             const ti_request_params* params, int chunk, const float* draws, int out_stride,
+                             int32_t* out_tokens, int32_t* out_len, float* out_logprobs);
 
 /* Teacher-forced scoring of a token sequence on the device (InferenceEngine::compute_logprobs,
  * inference_engine.cpp:873-954; Quantizer::validate_quantization_accuracy is built on it,

@@ -589,6 +589,32 @@ int ti_sample_step_ws(const float* logits, int ldl, int M, int V, float temperat
 int ti_lookahead_sample(const float* logits, int ldl, int R, int V, float temperature, int top_k, float top_p,
                         const float* draws, int draw_cap, const int32_t* state, const int32_t* cfg,
                         unsigned long long* argmax, float* logprobs, void* ws, ti_stream_t s);
+/* Per-row parameters (continuous batching with per-request settings, ti_engine.h ti_engine_serve_requests): one
+ * entry per stream row in DEVICE memory, read by the row's workgroup as block-uniform loads, so a captured launch
+ * bakes in the table's pointer and never its values.  The sampler reads temperature / top_k / top_p, the penalty
+ * step (ti_penalty_step_rows, below) the other three. */
+typedef struct ti_row_params {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  float repetition, presence, frequency;
+  int32_t reserved[2];         /* 0 */
+} ti_row_params;                /* 32 bytes (static_assert in kernels/sample.hip) */
+/* ti_sample_step / ti_sample_device with row m's temperature, top_k and top_p taken from rows[m] (device, [M]):
+ * the same kernel body, so a row's token and log p are bit for bit those of the scalar form launched with the
+ * row's three values (on the same instance, next sentence).  max_top_k is the host's bound on the table's top_k:
+ * up to TI_SAMPLE_MAX_K every row runs on the LDS instance and ws may be null; above it EVERY row runs on the
+ * workspace instance (ti_sample_device_ws's) and ws holds M * ti_sample_workspace_bytes(V, max_top_k) bytes.
+ * The launch cannot validate device memory: the kernel clamps a row's top_k into [1, min(V, max_top_k)] before
+ * anything is indexed by it; a temperature that is not > 0 (NaN included) or equal to 1 divides nothing and a
+ * top_p that is not < 1 cuts nothing, as in the scalar form.
+ * TI_ERR_ARG (nothing launched): ti_sample_step's / ti_sample_device's, null rows, max_top_k outside [1, V],
+ * max_top_k > TI_SAMPLE_MAX_K with a null ws. */
+int ti_sample_step_rows(const float* logits, int ldl, int M, int V, const ti_row_params* rows, int max_top_k,
+                        const float* draws, int draw_stride, const int32_t* step_ctr, int advance, const int32_t* n_in,
+                        unsigned long long* argmax, float* logprobs, void* ws, ti_stream_t s);
+int ti_sample_device_rows(const float* logits, int ldl, int M, int V, const ti_row_params* rows, int max_top_k,
+                          const float* draws, int32_t* tokens, float* logprobs, void* ws, ti_stream_t s);
 
 /* ------------------------------------- repetition / presence / frequency penalties
  * llama.cpp's llama_sampler_penalties_apply over a stream's whole context (penalty_last_n = -1), applied to a
@@ -636,6 +662,14 @@ typedef struct ti_penalty_args {
   const int32_t* carry;        /* [M], nullable */
 } ti_penalty_args;
 int ti_penalty_step(const ti_penalty_args* a, ti_stream_t s);
+/* ti_penalty_step with row m's repetition / presence / frequency taken from rows[m] (device, [M]; ti_row_params
+ * above) instead of the struct, whose three scalar values are ignored: the same token-noting rules and the same
+ * arithmetic, bit for bit, for a row that penalises.  A row whose values are exactly (1, 0, 0) -- a request that
+ * does not penalise, an idle slot -- or not valid (repetition not finite or not > 0, presence or frequency not
+ * finite: device memory the launch cannot check) does nothing at all: its logits and its counts / seen / n_seen
+ * keep their bits, the token the step fed is not noted.
+ * TI_ERR_ARG (nothing launched): ti_penalty_step's except the three values, and null rows. */
+int ti_penalty_step_rows(const ti_penalty_args* a, const ti_row_params* rows, ti_stream_t s);
 
 /* ------------------------------------------------------- token-automaton guided decoding
  * A guide is a deterministic automaton over token ids, state -> {token id -> next state} (ti_engine.h ti_guide

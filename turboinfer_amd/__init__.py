@@ -87,6 +87,22 @@ class PenaltyArgs(C.Structure):
                 ("out_stride", C.c_int32), ("carry", C.c_void_p)]
 
 
+class RowParams(C.Structure):
+    """ti_row_params (include/ti_hip.h): one stream row's sampler and penalty values in a device table, 32 bytes."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition", C.c_float),
+                ("presence", C.c_float), ("frequency", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class RequestParams(C.Structure):
+    """ti_request_params (include/ti_engine.h): one request of Engine.serve_requests, 32 bytes."""
+    _fields_ = [("max_new", C.c_int32), ("stop_token", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
+                ("top_p", C.c_float), ("repetition", C.c_float), ("presence", C.c_float), ("frequency", C.c_float)]
+
+    def __init__(self, max_new=1, stop_token=-1, temperature=1.0, top_k=1, top_p=1.0, repetition=1.0, presence=0.0,
+                 frequency=0.0):
+        super().__init__(max_new, stop_token, temperature, top_k, top_p, repetition, presence, frequency)
+
+
 class Guide(C.Structure):
     """ti_guide (include/ti_engine.h): a token automaton as CSR on the host."""
     _fields_ = [("n_states", C.c_int32), ("start", C.c_int32), ("row_ptr", C.c_void_p), ("tokens", C.c_void_p),
@@ -150,6 +166,7 @@ EXPORTED = [
     "ti_attn_decode_shared", "ti_attn_shared_workspace_bytes", "ti_engine_share_prefix", "ti_engine_shared_prefix",
     "ti_penalty_reset", "ti_penalty_step", "ti_penalize_logits", "ti_engine_set_penalties", "ti_engine_get_penalties",
     "ti_guide_reset", "ti_guide_step", "ti_guide_check", "ti_guide_apply", "ti_engine_set_guide", "ti_engine_guide_states",
+    "ti_sample_step_rows", "ti_sample_device_rows", "ti_penalty_step_rows", "ti_engine_serve_requests",
 ]
 
 _lib = None
@@ -306,6 +323,11 @@ def lib() -> C.CDLL:
             L.ti_guide_apply.argtypes = [C.POINTER(Guide), i32, i32, i32, vp, C.POINTER(C.c_int)]
             L.ti_engine_set_guide.argtypes = [vp, C.POINTER(Guide)]
             L.ti_engine_guide_states.argtypes = [vp, vp]
+        if hasattr(L, "ti_engine_serve_requests"):   # (older TI_LIB builds in A/B runs lack the per-request tables)
+            L.ti_sample_step_rows.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+            L.ti_sample_device_rows.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+            L.ti_penalty_step_rows.argtypes = [C.POINTER(PenaltyArgs), vp, vp]
+            L.ti_engine_serve_requests.argtypes = [vp, i32, vp, vp, C.POINTER(RequestParams), i32, vp, i32, vp, vp, vp]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -656,6 +678,28 @@ class Engine:
                                             temperature, top_k, top_p, _ptr(d), _ptr(out), _ptr(n), _ptr(lp)))
         return ([out[r, : n[r]].tolist() for r in range(len(prompts))],
                 [lp[r, : n[r]].copy() for r in range(len(prompts))])
+
+    def serve_requests(self, prompts, params, draws, chunk=16):
+        """ti_engine_serve_requests (continuous batching, every request with its own budget, stop token, sampler
+        values and penalties in one batch): params is one RequestParams, or dict of its fields, per request;
+        request r's t-th new token takes draws[r][t] (draws [n][>= every max_new]) -> (each request's new tokens,
+        each request's log-probabilities), in request order."""
+        n = len(prompts)
+        if len(params) != n:
+            raise ValueError(f"serve_requests: {n} prompts, {len(params)} params")
+        arr = (RequestParams * max(n, 1))()
+        for r, q in enumerate(params):
+            arr[r] = q if isinstance(q, RequestParams) else RequestParams(**q)
+        flat = np.ascontiguousarray([t for p in prompts for t in p], np.int32)
+        offs = np.ascontiguousarray(np.cumsum([0] + [len(p) for p in prompts]), np.int32)
+        d = np.ascontiguousarray(draws, np.float32).reshape(n, -1)
+        stride = d.shape[1]
+        out = np.zeros((n, stride), np.int32)
+        lp = np.zeros((n, stride), np.float32)
+        ln = np.zeros(n, np.int32)
+        check(lib().ti_engine_serve_requests(self.h, n, _ptr(flat), _ptr(offs), arr, chunk, _ptr(d), stride, _ptr(out),
+                                             _ptr(ln), _ptr(lp)))
+        return ([out[r, : ln[r]].tolist() for r in range(n)], [lp[r, : ln[r]].copy() for r in range(n)])
 
     def generate_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, start_pos=None):
         """ti_engine_generate_sampled: tokens [n][max_new] and log-probs [n][max_new]."""

@@ -121,6 +121,19 @@ int pen_reset_slot(ti_engine* e, int m, const int32_t* head, int n_head, const i
   return ti_penalty_reset(&e->pen, e->c.vocab, m, e->pen_ctx, n, e->s);
 }
 
+// The penalty state, made by whoever penalises first (ti_engine_set_penalties, ti_engine_serve_requests); the
+// buffers never move afterwards, so no graph has to go.
+int pen_state_alloc(ti_engine* e) {
+  if (e->pen.counts) return TI_OK;
+  const ti_engine_config& c = e->c;
+  TI_TRY(e->alloc_t(&e->pen.counts, (size_t)c.max_batch * c.vocab));
+  TI_TRY(e->alloc_t(&e->pen.seen, (size_t)c.max_batch * c.vocab));
+  TI_TRY(e->alloc_t(&e->pen.n_seen, (size_t)c.max_batch));
+  TI_TRY(e->alloc_t(&e->pen_ctx, (size_t)c.max_seq));
+  if (!e->pen_carry) TI_TRY(e->alloc_t(&e->pen_carry, (size_t)c.max_batch));   // (a guide may have made it)
+  return TI_OK;
+}
+
 // The entry points that produce tokens without the sampled step graph cannot penalise.
 int pen_refuse(const ti_engine* e, const char* fn) {
   if (!e->pen_active()) return TI_OK;
@@ -475,14 +488,7 @@ int ti_engine_set_penalties(ti_engine* e, float repetition, float presence, floa
   DeviceScope bind_(e);
   TI_TRY(drop_graphs(e));   // the step graphs bake the values in
   const bool on = repetition != 1.0f || presence != 0.0f || frequency != 0.0f;
-  if (on && !e->pen.counts) {
-    const ti_engine_config& c = e->c;
-    TI_TRY(e->alloc_t(&e->pen.counts, (size_t)c.max_batch * c.vocab));
-    TI_TRY(e->alloc_t(&e->pen.seen, (size_t)c.max_batch * c.vocab));
-    TI_TRY(e->alloc_t(&e->pen.n_seen, (size_t)c.max_batch));
-    TI_TRY(e->alloc_t(&e->pen_ctx, (size_t)c.max_seq));
-    if (!e->pen_carry) TI_TRY(e->alloc_t(&e->pen_carry, (size_t)c.max_batch));   // (a guide may have made it)
-  }
+  if (on) TI_TRY(pen_state_alloc(e));
   e->pen_rep = repetition;
   e->pen_pres = presence;
   e->pen_freq = frequency;

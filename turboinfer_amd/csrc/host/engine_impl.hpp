@@ -57,6 +57,10 @@ struct StepMode {
   bool sampled = false;   // ti_penalty_step / ti_guide_step (when active) + ti_sample_step behind the lm_head
   bool shared = false;    // the registered prefix attended once for all streams (ti_attn_decode_shared)
   bool carry = false;     // the penalty / guide step takes each slot's pen_carry token first (the serve loop's chunks)
+  // ti_engine_serve_requests: the launches behind the lm_head read each row's values from e->row_params
+  bool rows = false;      // ti_penalty_step_rows (with rows_pen) / ti_sample_step_rows instead of the scalar forms
+  bool rows_pen = false;  // rows: some request of the call penalises, the penalty launch is in the graph
+  bool rows_big = false;  // rows: some request's top_k is above TI_SAMPLE_MAX_K, every row on the workspace instance
 };
 
 // Everything a captured graph bakes in that can differ between two live graphs.  Whatever else enqueue_step or
@@ -68,6 +72,7 @@ struct GraphKey {
   int slot;     // Verify: the stream slot; Step: 0
   int splits;   // Verify: la_splits; Step: 0
   bool advance, sampled, shared, carry;
+  bool row_table, rows_pen, rows_big;   // StepMode's rows / rows_pen / rows_big, false in a Verify key
   auto operator<=>(const GraphKey&) const = default;
 };
 
@@ -173,6 +178,9 @@ struct ti_engine {
   int32_t* guide_state = nullptr;  // [max_batch] each slot's automaton state, -1 = free or dead
   std::vector<void*> guide_bufs;   // the live guide's device buffers, freed when it is replaced
   bool guide_active() const { return guide.mask != nullptr; }
+  // ti_engine_serve_requests: each slot's sampler and penalty values, read by the rows-mode step graphs
+  // (StepMode::rows), which bake in this pointer only.  Allocated by the first call, outside ti_engine_memory.
+  ti_row_params* row_params = nullptr;   // [max_batch]
   unsigned long long* argmax = nullptr;
   int32_t* pos = nullptr;
   int32_t* base_pos = nullptr;
@@ -361,6 +369,8 @@ int ensure_io(ti_engine* e, int in_cap, int out_cap);
 int read_argmax(ti_engine* e, int n, std::vector<unsigned long long>& keys);
 int grow_step_draws(ti_engine* e, int need);
 int sampler_prepare(ti_engine* e, float t, int k, float p, int ws_rows);
+int sampler_ws_reserve(ti_engine* e, size_t bytes);
+int pen_state_alloc(ti_engine* e);
 
 // ---- engine_generate.cpp
 int generate_impl(ti_engine* e, int n, const int32_t* prompts, const int32_t* lens, int stride, const int32_t* start_pos,

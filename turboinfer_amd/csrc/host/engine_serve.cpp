@@ -14,15 +14,26 @@ using namespace ti_eng;
 // A chunk's step s is every slot's draw index s (step_ctr 0, n_in 1), so before
 // the chunk each live slot's row of the [max_batch][draw_cap] draw buffer gets its request's next draws, and
 // after it the row of log-probabilities is read back.  With sp == null nothing of this is enqueued.
+//
+// ti_engine_serve_requests (sp->params != null) is the sampled loop with request r's budget, stop token, sampler
+// values and penalties its own: max_new is then the stride of the host arrays (>= every request's budget), the step
+// graph is the rows-mode one (StepMode::rows), and the slots' table e->row_params is copied before a chunk whenever
+// a slot changed hands.  With params == null nothing of this is enqueued either.
 struct ServeSampler {
   const float* draws;   // host [n_req][max_new]
   float* out_logprobs;  // host [n_req][max_new], nullable
+  const ti_request_params* params = nullptr;   // host [n_req], nullable
 };
+
+static bool penalises(const ti_request_params& q) { return q.repetition != 1.0f || q.presence != 0.0f || q.frequency != 0.0f; }
 
 static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
                       int max_new, int eos, int chunk, const ServeSampler* sp, int32_t* out_tokens, int32_t* out_len) {
   const ti_engine_config& c = e->c;
   const int B = c.max_batch;
+  const ti_request_params* rp = sp ? sp->params : nullptr;
+  auto budget = [&](int r) { return rp ? rp[r].max_new : max_new; };
+  auto stop = [&](int r) { return rp ? rp[r].stop_token : eos; };
   // A prefix registered for every slot (ti_engine_share_prefix with n_streams == max_batch): each prompt is the
   // continuation behind it, every slot -- idle ones too -- sits at or past P and never touches its copy of the
   // prefix, so a freed slot is reused without a new copy.  Registered for fewer slots: cleared.  P = 0: as ever.
@@ -31,14 +42,31 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
   int max_len = 1;
   for (int r = 0; r < n_req; ++r) {
     const int L = offsets[r + 1] - offsets[r];
-    if (L < 1 || P + L + max_new - 1 > c.max_seq)
-      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, P + L, max_new,
+    if (L < 1 || P + L + budget(r) - 1 > c.max_seq)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, P + L, budget(r),
                           c.max_seq);
     max_len = std::max(max_len, L);
   }
-  const bool pen = sp && e->pen_active();   // (the greedy loop is refused while they are active)
+  bool rows_pen = false, rows_big = false;   // some request penalises / has top_k above the LDS instance's
+  for (int r = 0; rp && r < n_req; ++r) {
+    rows_pen = rows_pen || penalises(rp[r]);
+    rows_big = rows_big || rp[r].top_k > TI_SAMPLE_MAX_K;
+  }
+  // (the greedy loop is refused while they are active; the rows loop has its own, the engine-wide ones do not apply)
+  const bool pen = rp ? rows_pen : sp && e->pen_active();
   const bool guide = sp && e->guide_active();
-  const StepMode mode{true, sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen || guide};
+  const StepMode mode{true, sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen || guide, rp != nullptr, rows_pen, rows_big};
+  auto slot_pen = [&](int r) { return rp ? penalises(rp[r]) : pen; };   // does the request in the slot penalise
+  if (rp) {   // what the rows-mode graphs bake in: the table, the penalty state, the workspace (only growth drops graphs)
+    if (!e->row_params) TI_TRY(e->alloc_t(&e->row_params, (size_t)B));
+    if (rows_pen) TI_TRY(pen_state_alloc(e));
+    if (rows_big) TI_TRY(sampler_ws_reserve(e, ti_sample_workspace_bytes(c.vocab, c.vocab) * (size_t)B));
+  }
+  ti_row_params idle{};
+  idle.temperature = idle.top_p = idle.repetition = 1.0f;
+  idle.top_k = 1;
+  std::vector<ti_row_params> table(rp ? B : 0, idle);
+  bool table_moved = rp != nullptr;   // a slot changed hands since the last copy
   std::vector<int32_t> carry(B, -1);
   TI_TRY(ensure_io(e, max_len, chunk + 1));
   for (int i = 0; i < n_req * max_new; ++i) out_tokens[i] = -1;
@@ -76,9 +104,18 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
         const int L = offsets[slot_req[m] + 1] - offsets[slot_req[m]];
         TI_TRY(prefill_tokens(e, m, L - 1, P));
         // the slot's histogram starts over: the registered prefix, then the whole prompt (its last token too)
-        if (pen) TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), P, prompts + offsets[slot_req[m]], L));
+        if (pen && slot_pen(slot_req[m])) TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), P, prompts + offsets[slot_req[m]], L));
         if (guide) TI_TRY(guide_start_slots(e, m, 1));   // a freed slot restarts at the guide's start state
+        if (rp) {
+          const ti_request_params& q = rp[slot_req[m]];
+          table[m] = ti_row_params{q.temperature, q.top_k, q.top_p, q.repetition, q.presence, q.frequency, {0, 0}};
+          table_moved = true;
+        }
       }
+    }
+    if (table_moved) {   // in stream order, like the draws: the graphs bake the pointer, never the values
+      TI_TRY(ti_memcpy_h2d(e->row_params, table.data(), table.size() * sizeof(ti_row_params), e->s));
+      table_moved = false;
     }
     if (pen || guide) {   // a continuing slot feeds a generated token the histogram / the automaton has not seen yet
       for (int m = 0; m < B; ++m) carry[m] = slot_req[m] >= 0 ? slot_tok[m] : -1;
@@ -103,7 +140,7 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
       for (int m = 0; m < B; ++m) {
         const int r = slot_req[m];
         if (r < 0) continue;
-        const int nd = std::min(S, max_new - out_len[r]);
+        const int nd = std::min(S, budget(r) - out_len[r]);
         std::memcpy(&dr[(size_t)m * e->draw_cap], sp->draws + (size_t)r * max_new + out_len[r], (size_t)nd * 4);
       }
       TI_TRY(ti_memcpy_h2d(e->draws, dr.data(), dr.size() * 4, e->s));
@@ -122,9 +159,13 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
         if (sp && sp->out_logprobs) sp->out_logprobs[(size_t)r * max_new + out_len[r]] = lp[(size_t)m * e->draw_cap + s];
         out_tokens[(size_t)r * max_new + out_len[r]++] = tok;
         slot_tok[m] = tok;
-        if (out_len[r] >= max_new || tok == eos) {
+        if (out_len[r] >= budget(r) || tok == stop(r)) {
           slot_req[m] = -1;
           --live;
+          if (rp) {   // the slot is idle until the next admission
+            table[m] = idle;
+            table_moved = true;
+          }
         }
       }
       if (slot_req[m] >= 0) slot_pos[m] += S;
@@ -167,6 +208,39 @@ int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, con
   TI_TRY(sampler_prepare(e, temperature, top_k, top_p, c.max_batch));
   const ServeSampler sp{draws, out_logprobs};
   return serve_loop(fn, e, n_req, prompts, offsets, max_new, eos, chunk, &sp, out_tokens, out_len);
+}
+
+int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                             const ti_request_params* params, int chunk, const float* draws, int out_stride,
+                             int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
+  const char* fn = "ti_engine_serve_requests";
+  if (!e || !prompts || !offsets || !draws || !out_tokens || !out_len || n_req < 1 || out_stride < 1 || chunk < 1)
+    return ti_set_error(TI_ERR_ARG, "%s: bad arguments", fn);
+  if (!params) return ti_set_error(TI_ERR_ARG, "%s: null params", fn);
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "%s: compat engine", fn);
+  // (the prefix the loop will treat prompts as continuations of: one registered for fewer slots is cleared there)
+  const int P = e->share_len > 0 && e->share_n == c.max_batch ? e->share_len : 0;
+  for (int r = 0; r < n_req; ++r) {   // (before the sampler's buffers move)
+    const ti_request_params& q = params[r];
+    const int L = offsets[r + 1] - offsets[r];
+    if (q.max_new < 1 || q.max_new > out_stride)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: max_new %d not in [1, out_stride %d]", fn, r, q.max_new, out_stride);
+    if (q.stop_token < -1 || q.stop_token >= c.vocab)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: stop_token %d not in [-1, vocab %d)", fn, r, q.stop_token, c.vocab);
+    if (q.top_k < 1 || q.top_k > c.vocab)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: top_k %d not in [1, vocab %d]", fn, r, q.top_k, c.vocab);
+    if (!(std::isfinite(q.repetition) && q.repetition > 0.0f) || !std::isfinite(q.presence) || !std::isfinite(q.frequency))
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: repetition %g (finite, > 0), presence %g, frequency %g (finite)", fn, r,
+                          (double)q.repetition, (double)q.presence, (double)q.frequency);
+    if (L < 1 || P + L + q.max_new - 1 > c.max_seq)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, P + L, q.max_new,
+                          c.max_seq);
+  }
+  TI_TRY(grow_step_draws(e, chunk));   // a chunk needs `chunk` draws per slot, as in ti_engine_serve_sampled
+  const ServeSampler sp{draws, out_logprobs, params};
+  return serve_loop(fn, e, n_req, prompts, offsets, out_stride, -1, chunk, &sp, out_tokens, out_len);
 }
 
 }  // extern "C"

@@ -329,7 +329,8 @@ int enqueue_step(ti_engine* e, int M, StepMode mode) {
   stamp_tag(TI_STAMP_TAG_LM_HEAD);
   TI_TRY(gemm(e->lm, e->h, TI_X_F32_RMSNORM, H, e->out_norm, el, 4, true));
   stamp_tag(TI_STAMP_TAG_OTHER);
-  if (mode.sampled && e->pen_active()) {   // the stream's context penalises the row the sampler is about to read
+  // (rows mode: the values are each row's own in e->row_params, the engine-wide ones do not apply)
+  if (mode.sampled && (mode.rows ? mode.rows_pen : e->pen_active())) {   // the stream's context penalises the row the sampler is about to read
     ti_penalty_args pa{};
     pa.logits = e->logits;
     pa.ldl = V;
@@ -346,11 +347,14 @@ int enqueue_step(ti_engine* e, int M, StepMode mode) {
     pa.out_tokens = e->out_tokens;
     pa.out_stride = e->out_cap;
     pa.carry = mode.carry ? e->pen_carry : nullptr;
-    TI_TRY(ti_penalty_step(&pa, e->s));
+    TI_TRY(mode.rows ? ti_penalty_step_rows(&pa, e->row_params, e->s) : ti_penalty_step(&pa, e->s));
   }
   if (mode.sampled && e->guide_active())   // the stream's automaton state masks the row (-inf survives the penalties)
     TI_TRY(guide_enqueue(e, M, mode));
-  if (mode.sampled)   // sample_next_token on the device; its key feeds the token back (ti_hip.h)
+  if (mode.sampled && mode.rows)   // each row's temperature / top_k / top_p from the table; one instance for all rows
+    TI_TRY(ti_sample_step_rows(e->logits, V, M, V, e->row_params, mode.rows_big ? V : std::min(V, TI_SAMPLE_MAX_K), e->draws,
+                               e->draw_cap, e->step_ctr, mode.advance, e->n_in, e->argmax, e->lps, e->samp_ws, e->s));
+  else if (mode.sampled)   // sample_next_token on the device; its key feeds the token back (ti_hip.h)
     TI_TRY(ti_sample_step_ws(e->logits, V, M, V, e->samp_t, e->samp_k, e->samp_p, e->draws, e->draw_cap, e->step_ctr,
                              mode.advance, e->n_in, e->argmax, e->lps, e->samp_ws, e->s));
   return TI_OK;
@@ -491,7 +495,8 @@ int drop_graphs(ti_engine* e) {
 
 // The step graph of M streams in `mode`: the key and the launches come from the one mode object.
 int get_graph(ti_engine* e, int M, StepMode mode, hipGraphExec_t* out) {
-  const GraphKey key{GraphKey::Step, M, 0, 0, mode.advance, mode.sampled, mode.shared, mode.carry};
+  const GraphKey key{GraphKey::Step, M, 0, 0, mode.advance, mode.sampled, mode.shared, mode.carry,
+                     mode.rows,      mode.rows_pen, mode.rows_big};
   return cached_graph(e, key, [&] { return enqueue_step(e, M, mode); }, out);
 }
 
@@ -521,6 +526,18 @@ int sampler_prepare(ti_engine* e, float t, int k, float p, int ws_rows) {
   e->samp_t = t;
   e->samp_k = k;
   e->samp_p = p;
+  return TI_OK;
+}
+
+// The sampler's workspace alone, for the rows-mode graphs (their parameters live in e->row_params, so samp_t / k / p
+// stay as the scalar graphs baked them): at least `bytes`, growing drops the graphs that bake the pointer in.
+int sampler_ws_reserve(ti_engine* e, size_t bytes) {
+  if (bytes <= e->samp_ws_bytes) return TI_OK;
+  TI_TRY(drop_graphs(e));
+  void* w = nullptr;
+  TI_TRY(e->alloc(&w, bytes));
+  e->samp_ws = w;
+  e->samp_ws_bytes = bytes;
   return TI_OK;
 }
 

@@ -29,7 +29,8 @@ __device__ __forceinline__ float pen_apply(float l, int count, float repetition,
   return a - d;
 }
 
-__global__ __launch_bounds__(kPenThreads) void penalty_step_kernel(const ti_penalty_args a) {
+// One stream's step with its three values (the kernel arguments, or the row's table entry)
+__device__ __forceinline__ void penalty_step_row(const ti_penalty_args& a, float repetition, float presence, float frequency) {
   __shared__ int s_n;
   const int m = blockIdx.x, tid = threadIdx.x;
   int t = 0;   // the row's draw index, as sample_kernel computes it
@@ -73,8 +74,25 @@ __global__ __launch_bounds__(kPenThreads) void penalty_step_kernel(const ti_pena
     for (int k = 0; k < kPenBatch; ++k) l[k] = c[k] > 0 ? lg[v[k]] : 0.0f;
 #pragma unroll
     for (int k = 0; k < kPenBatch; ++k)
-      if (c[k] > 0) lg[v[k]] = pen_apply(l[k], c[k], a.repetition, a.presence, a.frequency);
+      if (c[k] > 0) lg[v[k]] = pen_apply(l[k], c[k], repetition, presence, frequency);
   }
+}
+
+__global__ __launch_bounds__(kPenThreads) void penalty_step_kernel(const ti_penalty_args a) {
+  penalty_step_row(a, a.repetition, a.presence, a.frequency);
+}
+
+// finite: the exponent field is not all ones (a bit test, whatever the compiler assumes about NaNs)
+__device__ __forceinline__ bool pen_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+// ti_penalty_step_rows: the values are block-uniform loads from rows[m].  A row that does not penalise, or whose
+// entry ti_penalty_step would have refused, leaves before anything is read or written.
+__global__ __launch_bounds__(kPenThreads) void penalty_step_rows_kernel(const ti_penalty_args a, const ti_row_params* rows) {
+  const ti_row_params rp = rows[blockIdx.x];
+  const float rep = rp.repetition, pres = rp.presence, freq = rp.frequency;
+  if (rep == 1.0f && pres == 0.0f && freq == 0.0f) return;
+  if (!(pen_finite(rep) && rep > 0.0f) || !pen_finite(pres) || !pen_finite(freq)) return;
+  penalty_step_row(a, rep, pres, freq);
 }
 
 // counts / seen rows of the slot are zero and n_seen[m] is 0 on entry (the launcher's memsets)
@@ -105,6 +123,18 @@ extern "C" int ti_penalty_reset(const ti_penalty_state* st, int V, int m, const 
   const int blocks = (n + ti::kPenResetThreads - 1) / ti::kPenResetThreads;
   hipLaunchKernelGGL(ti::penalty_reset_kernel, dim3(blocks), dim3(ti::kPenResetThreads), 0, s, *st, V, m, tokens_dev, n);
   TI_LAUNCH_CHECK("penalty_reset_kernel");
+  return TI_OK;
+}
+
+extern "C" int ti_penalty_step_rows(const ti_penalty_args* a, const ti_row_params* rows, ti_stream_t stream) {
+  if (!a || !rows || !a->logits || !a->state.counts || !a->state.seen || !a->state.n_seen || (a->step_ctr && !a->out_tokens))
+    return ti_set_error(TI_ERR_ARG, "ti_penalty_step_rows: null");
+  if (a->M < 1 || a->V < 1 || a->ldl < a->V || a->draw_stride < 1 || a->out_stride < 0)
+    return ti_set_error(TI_ERR_ARG, "ti_penalty_step_rows: M %d V %d ldl %d draw_stride %d out_stride %d", a->M, a->V,
+                        a->ldl, a->draw_stride, a->out_stride);
+  hipLaunchKernelGGL(ti::penalty_step_rows_kernel, dim3(a->M), dim3(ti::kPenThreads), 0, (hipStream_t)stream, *a, rows);
+  TI_LAUNCH_CHECK("penalty_step_rows_kernel");
+  ti_stamp_next(ti::STAMP_OTHER, 0);   // (unstamped; keeps the stamped step's launch list whole)
   return TI_OK;
 }
 

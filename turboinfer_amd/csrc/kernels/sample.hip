@@ -54,7 +54,12 @@ struct SampArgs {
   int32_t lp_stride;
   char* ws;                    // top_k > TI_SAMPLE_MAX_K: per-row survivor arrays in HBM (ws_bytes each)
   size_t ws_bytes;
+  // sample_kernel<BIG, true> (ti_sample_step_rows): row m's temperature / top_k / top_p are rows[m]'s, the three
+  // scalars above unread; max_top_k is the host's bound that chose the instance
+  const ti_row_params* rows;   // device [M]
+  int32_t max_top_k;
 };
+static_assert(sizeof(ti_row_params) == 32, "ti_row_params: 32 bytes, the engine's table stride");
 
 // Survivor arrays of one row when they do not fit in LDS (top_k > TI_SAMPLE_MAX_K, up to V):
 // val f32[V], idx i32[V], p f32[V], sorted f32[V], rank i32[V] (each 16-byte aligned: the
@@ -109,7 +114,9 @@ __device__ int block_excl_scan(int v, int* total, int* s_w) {
 
 // BIG: top_k above TI_SAMPLE_MAX_K -- the survivor arrays live in the row's HBM workspace
 // (the same steps on them; the sequential sums read them from global memory).
-template <bool BIG>
+// ROWS: the three parameters are block-uniform loads from a.rows[m] instead of kernel arguments; everything behind
+// the loads is the one body, so a row's bits are those of the scalar instance with the same values.
+template <bool BIG, bool ROWS = false>
 __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) {
   constexpr int LK = BIG ? 1 : TI_SAMPLE_MAX_K;   // LDS survivor capacity
   __shared__ uint32_t hist[256];
@@ -128,7 +135,16 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
   __shared__ uint32_t s_ck[kCand];
   __shared__ int s_ci[kCand];
   __shared__ uint8_t s_cf[kCand];
-  const int m = blockIdx.x, tid = threadIdx.x, V = a.V, k = a.top_k;
+  const int m = blockIdx.x, tid = threadIdx.x, V = a.V;
+  float temperature = a.temperature, top_p = a.top_p;
+  int k = a.top_k;
+  if constexpr (ROWS) {
+    const ti_row_params rp = a.rows[m];
+    temperature = rp.temperature;
+    top_p = rp.top_p;
+    // device memory nobody validated: k indexes LDS and the workspace, so it is clamped before anything uses it
+    k = min(max(rp.top_k, 1), min(V, BIG ? a.max_top_k : min(a.max_top_k, TI_SAMPLE_MAX_K)));
+  }
   const int CAP = BIG ? V : TI_SAMPLE_MAX_K;
   float *s_val = l_val, *s_p = l_p, *s_sorted = l_sorted;
   int *s_idx = l_idx, *s_rank = l_rank;
@@ -144,8 +160,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
     s_key = (unsigned long long*)(w + 5 * A);
   }
   const float* row = a.logits + (size_t)m * a.ldl;
-  const bool temp = a.temperature != 1.0f && a.temperature > 0.0f;
-  auto lg = [&](int i) { return temp ? row[i] / a.temperature : row[i]; };
+  const bool temp = temperature != 1.0f && temperature > 0.0f;
+  auto lg = [&](int i) { return temp ? row[i] / temperature : row[i]; };
 
   int t = 0;   // which draw (and logprob slot) this step's token is
   size_t dm = (size_t)m * a.draw_stride;   // the row's draws
@@ -219,7 +235,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
             v[j] = i < g1 ? row[i] : 0.0f;
           }
 #pragma unroll
-          for (int j = 0; j < 8; ++j) rk[c * 8 + j] = samp_key(temp ? v[j] / a.temperature : v[j]);
+          for (int j = 0; j < 8; ++j) rk[c * 8 + j] = samp_key(temp ? v[j] / temperature : v[j]);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -240,7 +256,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int i = b + 64 * j + lane;
-        f(i, samp_key(temp ? v[j] / a.temperature : v[j]), i < g1);
+        f(i, samp_key(temp ? v[j] / temperature : v[j]), i < g1);
       }
     }
   };
@@ -321,7 +337,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
             for (int j = 0; j < U; ++j) v[j] = b + j * kSampThreads < V ? row[b + j * kSampThreads] : 0.0f;
 #pragma unroll
             for (int j = 0; j < U; ++j)
-              if (b + j * kSampThreads < V) f(samp_key(temp ? v[j] / a.temperature : v[j]));
+              if (b + j * kSampThreads < V) f(samp_key(temp ? v[j] / temperature : v[j]));
           }
         },
         k, &kth, &need_eq);
@@ -344,7 +360,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
       const bool keep = (ok && key > kth) || (eq && eq_run + below(me) < need_eq);
       const unsigned long long mk = __ballot(keep);
       if (keep && run + below(mk) < CAP) {
-        s_val[run + below(mk)] = temp ? row[i] / a.temperature : row[i];
+        s_val[run + below(mk)] = temp ? row[i] / temperature : row[i];
         s_idx[run + below(mk)] = i;
       }
       run += __popcll(mk);
@@ -421,7 +437,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
   // ---- top-p: rank by probability (descending, lower index first on ties), cut, renormalise.
   // Rank order = ascending (~bits(p), survivor position) for p >= 0: a bitonic sort of those
   // 64-bit keys in LDS, padded to a power of two with all-ones keys.
-  if (a.top_p < 1.0f) {
+  if (top_p < 1.0f) {
     int P = 64;
     while (P < n) P <<= 1;
     for (int i = tid; i < P; i += kSampThreads)
@@ -446,7 +462,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(const SampArgs a) 
     }
     __syncthreads();
     if (tid == 0) {
-      const int r = seq_find(s_sorted, a.top_p);
+      const int r = seq_find(s_sorted, top_p);
       s_cut = r < 0 ? n : r + 1;
     }
     __syncthreads();
@@ -510,6 +526,68 @@ static int sample_launch(ti::SampArgs a, int M, ti_stream_t stream) {
   TI_LAUNCH_CHECK("sample_kernel");
   ti_stamp_next(ti::STAMP_OTHER, 0);   // (unstamped; keeps the stamped step's launch list whole)
   return TI_OK;
+}
+
+// The per-row-table forms: one instance for all rows, chosen by the host's bound on the table's top_k.
+static int sample_launch_rows(ti::SampArgs a, int M, const char* fn, ti_stream_t stream) {
+  if (!a.logits || !a.draws || M < 1 || a.V < 1 || a.ldl < a.V || a.draw_stride < 1)
+    return ti_set_error(TI_ERR_ARG, "%s: bad arguments", fn);
+  if (!a.rows) return ti_set_error(TI_ERR_ARG, "%s: rows required", fn);
+  if (a.max_top_k < 1 || a.max_top_k > a.V)
+    return ti_set_error(TI_ERR_ARG, "%s: max_top_k %d not in [1, V = %d]", fn, a.max_top_k, a.V);
+  if (a.max_top_k > TI_SAMPLE_MAX_K) {
+    if (!a.ws)
+      return ti_set_error(TI_ERR_ARG, "%s: max_top_k %d > %d needs a workspace (ti_sample_workspace_bytes)", fn,
+                          a.max_top_k, TI_SAMPLE_MAX_K);
+    a.ws_bytes = ti::samp_ws_row_bytes(a.V);
+    hipLaunchKernelGGL((ti::sample_kernel<true, true>), dim3(M), dim3(ti::kSampThreads), 0, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL((ti::sample_kernel<false, true>), dim3(M), dim3(ti::kSampThreads), 0, (hipStream_t)stream, a);
+  }
+  TI_LAUNCH_CHECK("sample_kernel");
+  ti_stamp_next(ti::STAMP_OTHER, 0);   // (unstamped; keeps the stamped step's launch list whole)
+  return TI_OK;
+}
+
+extern "C" int ti_sample_device_rows(const float* logits, int ldl, int M, int V, const ti_row_params* rows, int max_top_k,
+                                     const float* draws, int32_t* tokens, float* logprobs, void* ws, ti_stream_t stream) {
+  ti::SampArgs a{};
+  a.ws = (char*)ws;
+  a.logits = logits;
+  a.ldl = ldl;
+  a.V = V;
+  a.rows = rows;
+  a.max_top_k = max_top_k;
+  a.draws = draws;
+  a.draw_stride = 1;
+  a.tokens = tokens;
+  a.logprobs = logprobs;
+  a.lp_stride = 1;
+  if (!tokens) return ti_set_error(TI_ERR_ARG, "ti_sample_device_rows: tokens required");
+  return sample_launch_rows(a, M, "ti_sample_device_rows", stream);
+}
+
+extern "C" int ti_sample_step_rows(const float* logits, int ldl, int M, int V, const ti_row_params* rows, int max_top_k,
+                                   const float* draws, int draw_stride, const int32_t* step_ctr, int advance,
+                                   const int32_t* n_in, unsigned long long* argmax, float* logprobs, void* ws,
+                                   ti_stream_t stream) {
+  ti::SampArgs a{};
+  a.ws = (char*)ws;
+  a.logits = logits;
+  a.ldl = ldl;
+  a.V = V;
+  a.rows = rows;
+  a.max_top_k = max_top_k;
+  a.draws = draws;
+  a.draw_stride = draw_stride;
+  a.step_ctr = step_ctr;
+  a.advance = advance;
+  a.n_in = n_in;
+  a.argmax = argmax;
+  a.logprobs = logprobs;
+  a.lp_stride = draw_stride;
+  if (!step_ctr || !argmax) return ti_set_error(TI_ERR_ARG, "ti_sample_step_rows: step_ctr and argmax required");
+  return sample_launch_rows(a, M, "ti_sample_step_rows", stream);
 }
 
 extern "C" int ti_sample_device_ws(const float* logits, int ldl, int M, int V, float temperature, int top_k,
