@@ -482,6 +482,8 @@ int ti_hbm_calibrate(size_t bytes, int reps, double* read_gbps, double* copy_gbp
  * One block per stream: picks the token of this step (prompt token while step < n_in[m],
  * else the previous step's argmax), records fed-back tokens, gathers the fp16 embedding row
  * into h (fp32), sets pos[m] = base_pos[m] + *step_ctr, clears argmax row m (all slots).
+ * The recorded token is the key's own, 0xFFFFFFFF - (key & 0xFFFFFFFF) as an int32 (-1 for a row with no key),
+ * while the gather reads row 0 for any token outside [0, vocab).
  * placeholder_first >= 0 selects the reference_compat placeholder embedding
  * 0.1f*((offset + i) % 100) (inference_engine.cpp:1444-1448, 1509-1512) with offset
  * placeholder_first on step 0 and 0 afterwards.

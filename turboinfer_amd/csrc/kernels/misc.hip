@@ -110,7 +110,11 @@ __device__ __forceinline__ void step_begin_body(const ti_step_args a) {
       const float v = h2f(e[i]);
       h[i] = v;
       if (a.fold_x) {   // the first projection's TI_X_F16_FOLDED input (ti_hip.h)
-        a.fold_x[(size_t)m * a.hidden + i] = f2h(v * a.fold_w[i]);
+        // the product rounded to fp32, then to fp16, as on the 16-byte path: without the barrier the compiler
+        // folds the two into v_fma_mixlo_f16, one rounding of the exact product, a different fp16 now and then
+        float p = v * a.fold_w[i];
+        asm volatile("" : "+v"(p));
+        a.fold_x[(size_t)m * a.hidden + i] = f2h(p);
         ss = fmaf(v, v, ss);
       }
     }
