@@ -99,6 +99,10 @@ int ti_engine_set_stop(ti_engine* e, int32_t token);
 /* Step-graph replays (decode steps, each covering every stream of its call) and prompt chunks
  * (prefill) this engine has run since it was created. */
 int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_chunks);
+/* The graph cache since creation: graphs captured into it (a step or verify graph the cache did not hold), and
+ * graphs dropped from it (a setter or a grown buffer changed something they bake in).  Two calls between which
+ * neither number moves replayed the graphs they found.  Either pointer may be null. */
+int ti_engine_graph_counters(ti_engine* e, uint64_t* captured, uint64_t* dropped);
 
 /* A prompt prefix shared by the streams of a batch (a system prompt, a few-shot header): prefilled once,
  * attended once per step for all streams (ti_attn_decode_shared, ti_hip.h).
@@ -204,7 +208,9 @@ typedef struct ti_guide {
  *   ti_engine_generate, ti_engine_serve, both lookahead calls and ti_engine_beam_search produce tokens and
  *     cannot follow a guide: TI_ERR_UNSUPPORTED, naming the function, before anything is enqueued.
  *   ti_engine_step, ti_engine_score, the replay / timing entry points return the model's own numbers.
- * One automaton per engine; a union automaton is the caller's way to several.  Any KV format.
+ * One automaton per engine through this call; requests that need different automata, or none, in one batch name
+ * guides of the engine's library instead (ti_engine_add_guide, ti_engine_serve_requests_guided, below).  Any KV
+ * format.
  * TI_ERR_ARG: null e, a guide ti_guide_check rejects for the engine's vocab.  TI_ERR_UNSUPPORTED: a compat engine. */
 int ti_engine_set_guide(ti_engine* e, const ti_guide* g);
 /* out [max_batch]: every slot's current state (-1 everywhere when no guide is set).  After a sampled call a
@@ -213,6 +219,25 @@ int ti_engine_set_guide(ti_engine* e, const ti_guide* g);
  * lock-step batch of unequal prompt lengths, or behind a stop token, a stream steps on to the batch's last step
  * and its state follows the tokens of those steps, which the call does not return. */
 int ti_engine_guide_states(ti_engine* e, int32_t* out);
+
+/* The guide library: up to TI_GUIDE_CAP guides live on the engine at once, and each request of
+ * ti_engine_serve_requests_guided names one by its handle, or none.  Handle h is entry h - 1 of a device table of
+ * ti_guide_dev descriptors (ti_hip.h ti_guide_step_rows), all-zero where unused; the step graphs bake in the
+ * table's pointer, never an entry, so neither call below drops a captured graph.
+ * ti_engine_add_guide validates g with ti_guide_check, builds the per-state allow-bitmask as ti_engine_set_guide
+ * does, uploads both (buffers outside what ti_engine_memory reports, as are the table and -- allocated by the
+ * first add when absent -- the slots' state row and carry row), takes the lowest free handle (1 .. TI_GUIDE_CAP,
+ * *out_handle) and writes that one table entry in stream order.  The host keeps the handle's `start`.
+ * ti_engine_remove_guide synchronises the stream, zeroes the entry (handle 0: every entry) and frees its buffers;
+ * a zeroed entry is inert.  ti_engine_guide_count: live handles.
+ * The library is inert until a request names a handle: no other entry point refuses, changes its launch list or
+ * reads it, and ti_engine_set_guide and its single guide are independent of it.
+ * TI_ERR_ARG: null e / g / out_handle / out, a guide ti_guide_check rejects for the engine's vocab, a full library,
+ * a handle outside [0, TI_GUIDE_CAP] or (other than 0) not live.  TI_ERR_UNSUPPORTED: add on a compat engine. */
+#define TI_GUIDE_CAP 64
+int ti_engine_add_guide(ti_engine* e, const ti_guide* g, int* out_handle);
+int ti_engine_remove_guide(ti_engine* e, int handle);
+int ti_engine_guide_count(ti_engine* e, int* out);
 
 /* InferenceEngine::generate_beam_search (inference_engine.cpp:830-871, 1912-2069): the
  * reference's beam loop (max-heap on log-probability, expansion by the beam_size most probable
@@ -255,7 +280,8 @@ int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, con
  * penalties, all of them through one loop and one batch (a greedy extraction next to a creative completion).
  * The launches between the lm_head and the feedback read each stream row's values from a device table
  * [max_batch] of ti_row_params (ti_hip.h: ti_penalty_step_rows, ti_guide_step when a guide is set -- the
- * engine's one guide, for every request, as in ti_engine_serve_sampled -- and ti_sample_step_rows).  The step
+ * engine's one guide, for every request, as in ti_engine_serve_sampled; per-request guides are
+ * ti_engine_serve_requests_guided's, below -- and ti_sample_step_rows).  The step
  * graph bakes in the table's pointer only; before a chunk that follows an admission or a departure the host
  * copies the table in stream order, as it does the draws (idle slots hold temperature 1, top_k 1, top_p 1,
  * penalties (1, 0, 0)).  So different parameters, within a call or between calls, drop no graph.
@@ -290,6 +316,28 @@ typedef struct ti_request_params {
 int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
                              const ti_request_params* params, int chunk, const float* draws, int out_stride,
                              int32_t* out_tokens, int32_t* out_len, float* out_logprobs);
+/* ti_engine_serve_requests with request r under the library guide guides[r] (host, [n_req]; a handle of
+ * ti_engine_add_guide, or 0 for none; guides nullable): the greedy extraction takes its JSON or choice-set automaton
+ * into the same batch as the creative completion that must not have one.  With a null guides, or every handle 0,
+ * the call IS ti_engine_serve_requests (which is this call with guides == NULL) and enqueues exactly what that does.
+ * When some request names a handle:
+ *   the slot's entry of the ti_row_params table carries the handle in reserved[0] (0 for an unguided request and
+ *     for an idle slot), and ti_guide_step_rows -- behind the penalty launch, before the sampler -- is in the
+ *     call's step graph (its own graph key, like the penalty launch's); the carry row is on;
+ *   at admission the slot's state is reset to the start state of the request's guide, or to -1 for a request
+ *     without one (ti_engine_guide_states then reads -1 for that slot);
+ *   the prompt, and a registered shared prefix before it, is not run through the automaton.
+ * Contract: request r's tokens and log-probabilities are bit for bit what ti_engine_serve_requests returns for r on
+ * a fresh engine of the same shape and max_batch with ti_engine_set_guide set to r's guide (no guide set for
+ * handle 0) -- whatever the other requests' guides and parameters, the slot and the chunking.  The workspace-instance
+ * exception of ti_engine_serve_requests holds unchanged.  Any KV format.
+ * TI_ERR_ARG before anything is enqueued, naming the request: ti_engine_serve_requests', a handle outside
+ * [0, TI_GUIDE_CAP], a handle that is not live.  TI_ERR_UNSUPPORTED: some request names a handle while
+ * ti_engine_set_guide's guide is set (one source of constraint per call); a compat engine. */
+int ti_engine_serve_requests_guided(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                                    const ti_request_params* params, const int32_t* guides, int chunk,
+                                    const float* draws, int out_stride, int32_t* out_tokens, int32_t* out_len,
+                                    float* out_logprobs);
 
 /* Teacher-forced scoring of a token sequence on the device (InferenceEngine::compute_logprobs,
  * inference_engine.cpp:873-954; Quantizer::validate_quantization_accuracy is built on it,

@@ -594,13 +594,13 @@ int ti_lookahead_sample(const float* logits, int ldl, int R, int V, float temper
 /* Per-row parameters (continuous batching with per-request settings, ti_engine.h ti_engine_serve_requests): one
  * entry per stream row in DEVICE memory, read by the row's workgroup as block-uniform loads, so a captured launch
  * bakes in the table's pointer and never its values.  The sampler reads temperature / top_k / top_p, the penalty
- * step (ti_penalty_step_rows, below) the other three. */
+ * step (ti_penalty_step_rows, below) the other three, the guide step (ti_guide_step_rows, below) reserved[0]. */
 typedef struct ti_row_params {
   float temperature;
   int32_t top_k;
   float top_p;
   float repetition, presence, frequency;
-  int32_t reserved[2];         /* 0 */
+  int32_t reserved[2];         /* [0]: the row's guide handle, 0 = none (ti_guide_step_rows); [1]: 0 */
 } ti_row_params;                /* 32 bytes (static_assert in kernels/sample.hip) */
 /* ti_sample_step / ti_sample_device with row m's temperature, top_k and top_p taken from rows[m] (device, [M]):
  * the same kernel body, so a row's token and log p are bit for bit those of the scalar form launched with the
@@ -718,6 +718,20 @@ typedef struct ti_guide_args {
   const int32_t* carry;        /* [M], nullable */
 } ti_guide_args;
 int ti_guide_step(const ti_guide_args* a, ti_stream_t s);
+/* ti_guide_step with row m's guide its own: guides is a DEVICE table of guide_cap descriptors, rows the device
+ * table [M] the sampler and the penalty step read, and row m's handle is rows[m].reserved[0] -- 0 = none, h in
+ * [1, guide_cap] = guides[h - 1].  a->guide is ignored.  The row's workgroup loads its handle and then the
+ * descriptor as block-uniform loads and runs ti_guide_step's body on it, so a row with a valid handle holds, bit
+ * for bit, in its logits row and its state word what ti_guide_step launched with that descriptor writes for that
+ * row (a state outside [0, n_states) of the row's OWN guide counts as -1).  A captured launch bakes in the two
+ * pointers and guide_cap, never an entry's values.  The table is memory the launch cannot validate: a handle
+ * <= 0 or > guide_cap, an entry with n_states < 1, with any null pointer (an unused entry is all-zero) or with
+ * mask_words != ceil(V / 32) makes the row do nothing at all -- logits and state word keep their bits, the fed
+ * token is not consumed.  Descriptors are only read.
+ * TI_ERR_ARG (nothing launched): ti_guide_step's except those on a->guide, null guides, null rows,
+ * guide_cap < 1. */
+int ti_guide_step_rows(const ti_guide_args* a, const ti_guide_dev* guides, int guide_cap, const ti_row_params* rows,
+                       ti_stream_t s);
 
 /* -------------------------------------------------------------- fp32 op level */
 /* y[r][n] (+)= sum_k a[r][k]*b[k][n], b the reference [K][N] fp32 layout, one fmaf per k

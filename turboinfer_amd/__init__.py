@@ -31,6 +31,7 @@ GEMM_MAX_ROWS = 1024                # TI_GEMM_MAX_ROWS (include/ti_hip.h)
 BITS_G32 = 32                       # TI_BITS_G32 (include/ti_hip.h): group-32 weights (GGUF Q4_0 / Q8_0)
 BITS_AFF = 64                       # TI_BITS_AFF: affine group-32 int4 (GGUF Q4_1), with BITS_G32 | 4
 BITS_KV8 = 128                      # TI_BITS_KV8: e4m3 KV cache, OR-ed into an engine's bits (any weight format)
+GUIDE_CAP = 64                      # TI_GUIDE_CAP (include/ti_engine.h): guides an engine's library holds at once
 SCALE_GROUP, SCALE_TENSOR, SCALE_UNIT = 0, 1, 2
 ROWS_CONCAT, ROWS_INTERLEAVE8 = 0, 1
 (W_Q, W_K, W_V, W_O, W_GATE, W_UP, W_DOWN, W_LM_HEAD, V_ATTN_NORM, V_FFN_NORM, V_OUT_NORM, E_EMBED) = range(12)
@@ -88,7 +89,8 @@ class PenaltyArgs(C.Structure):
 
 
 class RowParams(C.Structure):
-    """ti_row_params (include/ti_hip.h): one stream row's sampler and penalty values in a device table, 32 bytes."""
+    """ti_row_params (include/ti_hip.h): one stream row's sampler and penalty values in a device table, 32 bytes;
+    reserved[0] is the row's guide handle (guide_step_rows), 0 = none."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition", C.c_float),
                 ("presence", C.c_float), ("frequency", C.c_float), ("reserved", C.c_int32 * 2)]
 
@@ -167,6 +169,8 @@ EXPORTED = [
     "ti_penalty_reset", "ti_penalty_step", "ti_penalize_logits", "ti_engine_set_penalties", "ti_engine_get_penalties",
     "ti_guide_reset", "ti_guide_step", "ti_guide_check", "ti_guide_apply", "ti_engine_set_guide", "ti_engine_guide_states",
     "ti_sample_step_rows", "ti_sample_device_rows", "ti_penalty_step_rows", "ti_engine_serve_requests",
+    "ti_guide_step_rows", "ti_engine_add_guide", "ti_engine_remove_guide", "ti_engine_guide_count",
+    "ti_engine_serve_requests_guided", "ti_engine_graph_counters",
 ]
 
 _lib = None
@@ -328,6 +332,14 @@ def lib() -> C.CDLL:
             L.ti_sample_device_rows.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
             L.ti_penalty_step_rows.argtypes = [C.POINTER(PenaltyArgs), vp, vp]
             L.ti_engine_serve_requests.argtypes = [vp, i32, vp, vp, C.POINTER(RequestParams), i32, vp, i32, vp, vp, vp]
+        if hasattr(L, "ti_guide_step_rows"):   # (older TI_LIB builds in A/B runs lack the guide library)
+            L.ti_guide_step_rows.argtypes = [C.POINTER(GuideArgs), vp, i32, vp, vp]
+            L.ti_engine_add_guide.argtypes = [vp, C.POINTER(Guide), C.POINTER(C.c_int)]
+            L.ti_engine_remove_guide.argtypes = [vp, i32]
+            L.ti_engine_guide_count.argtypes = [vp, C.POINTER(C.c_int)]
+            L.ti_engine_graph_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            L.ti_engine_serve_requests_guided.argtypes = [vp, i32, vp, vp, C.POINTER(RequestParams), vp, i32, vp, i32, vp,
+                                                          vp, vp]
         if hasattr(L, "ti_gemm_onerow_epi_launches"):   # (older TI_LIB builds in A/B runs lack it)
             L.ti_gemm_onerow_epi_launches.argtypes = []
             L.ti_gemm_onerow_epi_launches.restype = u64
@@ -522,6 +534,13 @@ def guide_apply(guide, state, fed_token, logits):
     return s.value, lg
 
 
+def guide_step_rows(args: GuideArgs, guides: DeviceBuffer, guide_cap: int, rows: DeviceBuffer, stream=None) -> None:
+    """ti_guide_step_rows: ti_guide_step with row m's guide its own -- `guides` a device table of guide_cap GuideDev
+    descriptors, `rows` the device table [M] of RowParams whose reserved[0] is the row's handle (0 = none, h =
+    guides[h - 1]); args.guide is ignored.  A row without a valid handle and descriptor keeps every bit."""
+    check(lib().ti_guide_step_rows(C.byref(args), guides.ptr, guide_cap, rows.ptr, stream))
+
+
 def logprob_rows(logits: DeviceBuffer, ld: int, rows: int, vocab: int, targets: DeviceBuffer,
                  out_logprob: DeviceBuffer, out_top1: DeviceBuffer | None = None, stream=None) -> None:
     """ti_logprob_rows over device buffers: logits fp32 [rows][ld], targets int32 [rows] (-1 = none) ->
@@ -679,14 +698,17 @@ class Engine:
         return ([out[r, : n[r]].tolist() for r in range(len(prompts))],
                 [lp[r, : n[r]].copy() for r in range(len(prompts))])
 
-    def serve_requests(self, prompts, params, draws, chunk=16):
+    def serve_requests(self, prompts, params, draws, chunk=16, guides=None):
         """ti_engine_serve_requests (continuous batching, every request with its own budget, stop token, sampler
         values and penalties in one batch): params is one RequestParams, or dict of its fields, per request;
         request r's t-th new token takes draws[r][t] (draws [n][>= every max_new]) -> (each request's new tokens,
-        each request's log-probabilities), in request order."""
+        each request's log-probabilities), in request order.  guides: per request a handle of add_guide, or 0 for
+        none (ti_engine_serve_requests_guided); None calls ti_engine_serve_requests itself."""
         n = len(prompts)
         if len(params) != n:
             raise ValueError(f"serve_requests: {n} prompts, {len(params)} params")
+        if guides is not None and len(guides) != n:
+            raise ValueError(f"serve_requests: {n} prompts, {len(guides)} guide handles")
         arr = (RequestParams * max(n, 1))()
         for r, q in enumerate(params):
             arr[r] = q if isinstance(q, RequestParams) else RequestParams(**q)
@@ -697,8 +719,13 @@ class Engine:
         out = np.zeros((n, stride), np.int32)
         lp = np.zeros((n, stride), np.float32)
         ln = np.zeros(n, np.int32)
-        check(lib().ti_engine_serve_requests(self.h, n, _ptr(flat), _ptr(offs), arr, chunk, _ptr(d), stride, _ptr(out),
-                                             _ptr(ln), _ptr(lp)))
+        if guides is None:
+            check(lib().ti_engine_serve_requests(self.h, n, _ptr(flat), _ptr(offs), arr, chunk, _ptr(d), stride, _ptr(out),
+                                                 _ptr(ln), _ptr(lp)))
+        else:
+            gh = np.ascontiguousarray(guides, np.int32).reshape(-1)
+            check(lib().ti_engine_serve_requests_guided(self.h, n, _ptr(flat), _ptr(offs), arr, _ptr(gh), chunk, _ptr(d),
+                                                        stride, _ptr(out), _ptr(ln), _ptr(lp)))
         return ([out[r, : ln[r]].tolist() for r in range(n)], [lp[r, : ln[r]].copy() for r in range(n)])
 
     def generate_sampled(self, prompts, max_new, temperature, top_k, top_p, draws, start_pos=None):
@@ -766,6 +793,24 @@ class Engine:
         g, _keep = make_guide(row_ptr, tokens, next, start)
         check(lib().ti_engine_set_guide(self.h, C.byref(g)))
 
+    def add_guide(self, row_ptr, tokens, next, start=0) -> int:
+        """ti_engine_add_guide: the automaton (as set_guide takes it) joins the engine's guide library -> its handle,
+        1 .. GUIDE_CAP, for serve_requests(guides=...).  No captured graph is dropped."""
+        g, _keep = make_guide(row_ptr, tokens, next, start)
+        h = C.c_int(0)
+        check(lib().ti_engine_add_guide(self.h, C.byref(g), C.byref(h)))
+        return h.value
+
+    def remove_guide(self, handle=0) -> None:
+        """ti_engine_remove_guide: the handle's guide leaves the library (0: all of them)."""
+        check(lib().ti_engine_remove_guide(self.h, handle))
+
+    def guide_count(self) -> int:
+        """Live handles of the guide library (ti_engine_guide_count)."""
+        n = C.c_int(0)
+        check(lib().ti_engine_guide_count(self.h, C.byref(n)))
+        return n.value
+
     def guide_states(self) -> np.ndarray:
         """int32 [max_batch]: every slot's automaton state, -1 = free or dead (ti_engine_guide_states)."""
         out = np.empty(self.cfg.max_batch, np.int32)
@@ -782,6 +827,13 @@ class Engine:
         """(decode step-graph replays, prefill chunks) run by this engine (ti_engine_counters)."""
         a, b = C.c_uint64(0), C.c_uint64(0)
         check(lib().ti_engine_counters(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def graph_counters(self):
+        """(graphs captured into the engine's cache, graphs dropped from it) since creation
+        (ti_engine_graph_counters): neither moves between two calls that replayed the graphs they found."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib().ti_engine_graph_counters(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
     def set_fold(self, on=None) -> bool:

@@ -510,6 +510,13 @@ int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_c
   return TI_OK;
 }
 
+int ti_engine_graph_counters(ti_engine* e, uint64_t* captured, uint64_t* dropped) {
+  if (!e) return ti_set_error(TI_ERR_ARG, "ti_engine_graph_counters: null");
+  if (captured) *captured = e->n_graphs_captured;
+  if (dropped) *dropped = e->n_graphs_dropped;
+  return TI_OK;
+}
+
 int ti_engine_prefill_attn_name(ti_engine* e, int rows, char* buf, int len) {
   if (!e || !buf || rows < 1 || len < 1) return ti_set_error(TI_ERR_ARG, "ti_engine_prefill_attn_name: null engine / buffer, rows or len < 1");
   if (e->c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_prefill_attn_name: compat engine");

@@ -61,6 +61,7 @@ struct StepMode {
   bool rows = false;      // ti_penalty_step_rows (with rows_pen) / ti_sample_step_rows instead of the scalar forms
   bool rows_pen = false;  // rows: some request of the call penalises, the penalty launch is in the graph
   bool rows_big = false;  // rows: some request's top_k is above TI_SAMPLE_MAX_K, every row on the workspace instance
+  bool rows_guide = false;  // rows: some request names a library guide, ti_guide_step_rows is in the graph
 };
 
 // Everything a captured graph bakes in that can differ between two live graphs.  Whatever else enqueue_step or
@@ -73,6 +74,7 @@ struct GraphKey {
   int splits;   // Verify: la_splits; Step: 0
   bool advance, sampled, shared, carry;
   bool row_table, rows_pen, rows_big;   // StepMode's rows / rows_pen / rows_big, false in a Verify key
+  bool rows_guide;                      // StepMode's rows_guide, false in a Verify key
   auto operator<=>(const GraphKey&) const = default;
 };
 
@@ -178,6 +180,17 @@ struct ti_engine {
   int32_t* guide_state = nullptr;  // [max_batch] each slot's automaton state, -1 = free or dead
   std::vector<void*> guide_bufs;   // the live guide's device buffers, freed when it is replaced
   bool guide_active() const { return guide.mask != nullptr; }
+  // ti_engine_add_guide (engine_guide.cpp): the guide library of ti_engine_serve_requests_guided.  Handle h is entry
+  // h - 1 of a device table [TI_GUIDE_CAP] of descriptors, all-zero where unused; the rows_guide step graphs bake in
+  // the table's pointer only (ti_guide_step_rows), so adding and removing guides drops no graph.  Allocated by the
+  // first add, outside ti_engine_memory; nothing but a request that names a handle reads it.
+  struct LibGuide {
+    bool live = false;
+    int start = 0;
+    std::vector<void*> bufs;   // the entry's CSR and bitmask on the device
+  };
+  ti_guide_dev* guide_table = nullptr;   // device [TI_GUIDE_CAP]
+  std::vector<LibGuide> guide_lib;       // host [TI_GUIDE_CAP] once the table exists
   // ti_engine_serve_requests: each slot's sampler and penalty values, read by the rows-mode step graphs
   // (StepMode::rows), which bake in this pointer only.  Allocated by the first call, outside ti_engine_memory.
   ti_row_params* row_params = nullptr;   // [max_batch]
@@ -194,6 +207,7 @@ struct ti_engine {
   int32_t stop_token = -1;
   uint64_t n_decode_steps = 0;   // step-graph replays (ti_engine_counters)
   uint64_t n_prefill_chunks = 0; // prompt chunks through enqueue_prefill
+  uint64_t n_graphs_captured = 0, n_graphs_dropped = 0;   // the graph cache's misses and drops (ti_engine_graph_counters)
   int splits_max = 1;
   int64_t kv_stride = 0;         // elements between the stream slots of a layer cache
   // TI_BITS_KV8 (taken out of c.bits at creation, which then holds the weight format alone): the
@@ -268,6 +282,8 @@ struct ti_engine {
     for (auto& g : graphs) hipGraphExecDestroy(g.second);
     for (void* p : allocs) hipFree(p);
     for (void* p : guide_bufs) hipFree(p);
+    for (auto& g : guide_lib)
+      for (void* p : g.bufs) hipFree(p);
     if (s) hipStreamDestroy(s);
   }
 };
@@ -320,6 +336,7 @@ int pen_refuse(const ti_engine* e, const char* fn);
 int guide_refuse(const ti_engine* e, const char* fn);
 int guide_start_slots(ti_engine* e, int first, int count);
 int guide_enqueue(ti_engine* e, int M, StepMode mode);
+int guide_reset_slot(ti_engine* e, int slot, int handle);
 
 // ---- engine_step.cpp: projections, attention routing, the step plan and its epilogues
 bool packed_rows(const ti_engine* e, int M);

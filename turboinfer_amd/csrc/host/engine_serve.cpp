@@ -19,10 +19,16 @@ using namespace ti_eng;
 // values and penalties its own: max_new is then the stride of the host arrays (>= every request's budget), the step
 // graph is the rows-mode one (StepMode::rows), and the slots' table e->row_params is copied before a chunk whenever
 // a slot changed hands.  With params == null nothing of this is enqueued either.
+//
+// ti_engine_serve_requests_guided (sp->guides != null) is the rows loop with request r under the library guide
+// guides[r] (engine_guide.cpp; 0 = none): when some request names one (StepMode::rows_guide) the slot's table entry
+// carries the handle, ti_guide_step_rows is in the graph, and a slot's state is reset at admission to its guide's
+// start or to -1.  With no handle named nothing of this is enqueued.
 struct ServeSampler {
   const float* draws;   // host [n_req][max_new]
   float* out_logprobs;  // host [n_req][max_new], nullable
   const ti_request_params* params = nullptr;   // host [n_req], nullable
+  const int32_t* guides = nullptr;             // host [n_req] library handles (0 = none), nullable; with params only
 };
 
 static bool penalises(const ti_request_params& q) { return q.repetition != 1.0f || q.presence != 0.0f || q.frequency != 0.0f; }
@@ -47,15 +53,21 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
                           c.max_seq);
     max_len = std::max(max_len, L);
   }
-  bool rows_pen = false, rows_big = false;   // some request penalises / has top_k above the LDS instance's
+  const int32_t* gh = rp ? sp->guides : nullptr;
+  // some request penalises / has top_k above the LDS instance's / names a library guide
+  bool rows_pen = false, rows_big = false, rows_guide = false;
   for (int r = 0; rp && r < n_req; ++r) {
     rows_pen = rows_pen || penalises(rp[r]);
     rows_big = rows_big || rp[r].top_k > TI_SAMPLE_MAX_K;
+    rows_guide = rows_guide || (gh && gh[r] > 0);
   }
   // (the greedy loop is refused while they are active; the rows loop has its own, the engine-wide ones do not apply)
   const bool pen = rp ? rows_pen : sp && e->pen_active();
-  const bool guide = sp && e->guide_active();
-  const StepMode mode{true, sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen || guide, rp != nullptr, rows_pen, rows_big};
+  // (the engine's one guide, or each request's own out of the library: the entry point refuses both in one call)
+  const bool guide = sp && (rows_guide || e->guide_active());
+  const StepMode mode{true,     sp != nullptr, P > 0 && B >= 2 && P >= e->share_min, pen || guide, rp != nullptr, rows_pen,
+                      rows_big, rows_guide};
+  auto slot_guide = [&](int r) { return rows_guide ? gh[r] : 0; };   // the handle the request's slot carries
   auto slot_pen = [&](int r) { return rp ? penalises(rp[r]) : pen; };   // does the request in the slot penalise
   if (rp) {   // what the rows-mode graphs bake in: the table, the penalty state, the workspace (only growth drops graphs)
     if (!e->row_params) TI_TRY(e->alloc_t(&e->row_params, (size_t)B));
@@ -105,10 +117,12 @@ static int serve_loop(const char* fn, ti_engine* e, int n_req, const int32_t* pr
         TI_TRY(prefill_tokens(e, m, L - 1, P));
         // the slot's histogram starts over: the registered prefix, then the whole prompt (its last token too)
         if (pen && slot_pen(slot_req[m])) TI_TRY(pen_reset_slot(e, m, e->share_tokens.data(), P, prompts + offsets[slot_req[m]], L));
-        if (guide) TI_TRY(guide_start_slots(e, m, 1));   // a freed slot restarts at the guide's start state
+        // a freed slot restarts at the guide's start state; the request's own guide's, or free without one
+        if (guide) TI_TRY(rows_guide ? guide_reset_slot(e, m, gh[slot_req[m]]) : guide_start_slots(e, m, 1));
         if (rp) {
           const ti_request_params& q = rp[slot_req[m]];
-          table[m] = ti_row_params{q.temperature, q.top_k, q.top_p, q.repetition, q.presence, q.frequency, {0, 0}};
+          table[m] = ti_row_params{q.temperature, q.top_k, q.top_p, q.repetition, q.presence, q.frequency,
+                                   {slot_guide(slot_req[m]), 0}};
           table_moved = true;
         }
       }
@@ -210,10 +224,12 @@ int ti_engine_serve_sampled(ti_engine* e, int n_req, const int32_t* prompts, con
   return serve_loop(fn, e, n_req, prompts, offsets, max_new, eos, chunk, &sp, out_tokens, out_len);
 }
 
-int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
-                             const ti_request_params* params, int chunk, const float* draws, int out_stride,
-                             int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
-  const char* fn = "ti_engine_serve_requests";
+}  // extern "C"
+
+// ti_engine_serve_requests (guides null) and ti_engine_serve_requests_guided
+static int serve_requests(const char* fn, ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                          const ti_request_params* params, const int32_t* guides, int chunk, const float* draws,
+                          int out_stride, int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
   if (!e || !prompts || !offsets || !draws || !out_tokens || !out_len || n_req < 1 || out_stride < 1 || chunk < 1)
     return ti_set_error(TI_ERR_ARG, "%s: bad arguments", fn);
   if (!params) return ti_set_error(TI_ERR_ARG, "%s: null params", fn);
@@ -238,9 +254,35 @@ int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, co
       return ti_set_error(TI_ERR_ARG, "%s: request %d: %d prompt + %d new tokens exceed max_seq %d", fn, r, P + L, q.max_new,
                           c.max_seq);
   }
+  for (int r = 0; guides && r < n_req; ++r) {
+    const int h = guides[r];
+    if (h < 0 || h > TI_GUIDE_CAP)
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: guide handle %d not in [0, TI_GUIDE_CAP %d]", fn, r, h, TI_GUIDE_CAP);
+    if (h > 0 && (e->guide_lib.empty() || !e->guide_lib[h - 1].live))
+      return ti_set_error(TI_ERR_ARG, "%s: request %d: guide handle %d is not live (ti_engine_add_guide)", fn, r, h);
+    if (h > 0 && e->guide_active())
+      return ti_set_error(TI_ERR_UNSUPPORTED, "%s: request %d names guide handle %d (ti_engine_add_guide) while the engine's "
+                          "guide is set (ti_engine_set_guide): one source of constraint per call", fn, r, h);
+  }
   TI_TRY(grow_step_draws(e, chunk));   // a chunk needs `chunk` draws per slot, as in ti_engine_serve_sampled
-  const ServeSampler sp{draws, out_logprobs, params};
+  const ServeSampler sp{draws, out_logprobs, params, guides};
   return serve_loop(fn, e, n_req, prompts, offsets, out_stride, -1, chunk, &sp, out_tokens, out_len);
+}
+
+extern "C" {
+
+int ti_engine_serve_requests(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                             const ti_request_params* params, int chunk, const float* draws, int out_stride,
+                             int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
+  return serve_requests("ti_engine_serve_requests", e, n_req, prompts, offsets, params, nullptr, chunk, draws, out_stride,
+                        out_tokens, out_len, out_logprobs);
+}
+
+int ti_engine_serve_requests_guided(ti_engine* e, int n_req, const int32_t* prompts, const int32_t* offsets,
+                                    const ti_request_params* params, const int32_t* guides, int chunk, const float* draws,
+                                    int out_stride, int32_t* out_tokens, int32_t* out_len, float* out_logprobs) {
+  return serve_requests("ti_engine_serve_requests_guided", e, n_req, prompts, offsets, params, guides, chunk, draws,
+                        out_stride, out_tokens, out_len, out_logprobs);
 }
 
 }  // extern "C"

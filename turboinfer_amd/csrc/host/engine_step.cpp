@@ -349,8 +349,8 @@ int enqueue_step(ti_engine* e, int M, StepMode mode) {
     pa.carry = mode.carry ? e->pen_carry : nullptr;
     TI_TRY(mode.rows ? ti_penalty_step_rows(&pa, e->row_params, e->s) : ti_penalty_step(&pa, e->s));
   }
-  if (mode.sampled && e->guide_active())   // the stream's automaton state masks the row (-inf survives the penalties)
-    TI_TRY(guide_enqueue(e, M, mode));
+  // the stream's automaton state masks the row (-inf survives the penalties); rows_guide: each row's own library guide
+  if (mode.sampled && (mode.rows_guide || e->guide_active())) TI_TRY(guide_enqueue(e, M, mode));
   if (mode.sampled && mode.rows)   // each row's temperature / top_k / top_p from the table; one instance for all rows
     TI_TRY(ti_sample_step_rows(e->logits, V, M, V, e->row_params, mode.rows_big ? V : std::min(V, TI_SAMPLE_MAX_K), e->draws,
                                e->draw_cap, e->step_ctr, mode.advance, e->n_in, e->argmax, e->lps, e->samp_ws, e->s));
@@ -480,6 +480,7 @@ int cached_graph(ti_engine* e, const GraphKey& key, const std::function<int()>& 
     hipGraphExec_t ex = nullptr;
     TI_TRY(capture_graph(e, enqueue, &ex));
     it = e->graphs.emplace(key, ex).first;
+    ++e->n_graphs_captured;
   }
   *out = it->second;
   return TI_OK;
@@ -489,6 +490,7 @@ int cached_graph(ti_engine* e, const GraphKey& key, const std::function<int()>& 
 int drop_graphs(ti_engine* e) {
   TI_TRY(ti_stream_sync(e->s));
   for (auto& g : e->graphs) hipGraphExecDestroy(g.second);
+  e->n_graphs_dropped += e->graphs.size();
   e->graphs.clear();
   return TI_OK;
 }
@@ -496,7 +498,7 @@ int drop_graphs(ti_engine* e) {
 // The step graph of M streams in `mode`: the key and the launches come from the one mode object.
 int get_graph(ti_engine* e, int M, StepMode mode, hipGraphExec_t* out) {
   const GraphKey key{GraphKey::Step, M, 0, 0, mode.advance, mode.sampled, mode.shared, mode.carry,
-                     mode.rows,      mode.rows_pen, mode.rows_big};
+                     mode.rows,      mode.rows_pen, mode.rows_big, mode.rows_guide};
   return cached_graph(e, key, [&] { return enqueue_step(e, M, mode); }, out);
 }
 
