@@ -36,6 +36,11 @@ $(BUILD)/k_gemv.o: turboinfer_amd/csrc/kernels/gemv.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -mllvm -amdgpu-kernarg-preload-count=16 -c $< -o $@
 
+# gemm_w8: the fused INT8 kernel's rounding sequence (no fp contraction); scalar fp32 FMAs only
+$(BUILD)/k_gemm_w8.o: turboinfer_amd/csrc/kernels/gemm_w8.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
 $(BUILD)/k_attention.o: turboinfer_amd/csrc/kernels/attention.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@

@@ -300,6 +300,21 @@ int ti_gemm_fold_partials(int bits, int M, int N, int K);
  * [b * (N / 16) / grid, (b + 1) * (N / 16) / grid)); *ntl is 1..8.  For tests that mean to run one
  * instance of the kernel.  TI_ERR_UNSUPPORTED when the call would take another kernel. */
 int ti_gemm_mb_plan(int bits, int M, int N, int K, int* grid, int* ntl);
+/* INT8 rows above 16.  ti_gemm_wq_a16 with bits 8 (group 128), TI_X_F16 rows and 17 <= M <=
+ * TI_GEMM_MAX_ROWS runs gemm_w8_kernel: one launch, the fused kernel's INT8 arithmetic, every epilogue kind,
+ * any M in the range (K % 128 == 0, K <= 65535, N % 16 == 0; tiles, x and out 16-byte aligned, ldx % 8 == 0
+ * and ldo % 4 == 0, else TI_ERR_UNSUPPORTED: every access of the kernel is a vector access).  The caller normalises
+ * TI_X_F32_RMSNORM inputs with ti_rmsnorm_f16 first, as for int4.  Still TI_ERR_UNSUPPORTED on this route:
+ * out_packed, TI_X_F16_PACKED rows, fold_x / a folded input (ss_in), and 8 | TI_BITS_G32 (Q8_0 keeps its
+ * 16-row fused pieces).  ti_gemm_max_rows and ti_gemm_packed_rows[_for] are unchanged: they describe the
+ * fused kernel and the int4 packed route.
+ * ti_gemm_w8_rows: 1 when an M x N x K call of that kind takes gemm_w8_kernel, 0 otherwise -- also for every
+ * M once the process runs with TI_GEMM_W8_ROWS=0 (read once), which restores the refusal above 16 rows.
+ * ti_gemm_w8_plan: the instance such a call launches -- 16 *rb rows per workgroup (rb 2 or 4), *tpw weight
+ * tiles per wave, *kwaves k-waves (8 / *kwaves column-waves; K is split inside the workgroup only, summed in
+ * k-wave order) and *grid workgroups.  TI_ERR_UNSUPPORTED when ti_gemm_w8_rows is 0. */
+int ti_gemm_w8_rows(int M, int N, int K);
+int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

@@ -171,6 +171,7 @@ EXPORTED = [
     "ti_sample_step_rows", "ti_sample_device_rows", "ti_penalty_step_rows", "ti_engine_serve_requests",
     "ti_guide_step_rows", "ti_engine_add_guide", "ti_engine_remove_guide", "ti_engine_guide_count",
     "ti_engine_serve_requests_guided", "ti_engine_graph_counters",
+    "ti_gemm_w8_rows", "ti_gemm_w8_plan",
 ]
 
 _lib = None
@@ -216,6 +217,9 @@ def lib() -> C.CDLL:
         L.ti_gemm_packed_rows_for.argtypes = [i32, i32, i32, i32]
         L.ti_gemm_tile_plan.argtypes = [i32, i32, i32, i32, C.c_int64, vp, vp, vp]
         L.ti_gemm_mb_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "ti_gemm_w8_rows"):   # (older TI_LIB builds in A/B runs lack the INT8 rows kernel)
+            L.ti_gemm_w8_rows.argtypes = [i32, i32, i32]
+            L.ti_gemm_w8_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
         L.ti_rmsnorm_f16.argtypes = [vp, i32, vp, f32, vp, i32, i32, i32, vp]
         L.ti_rmsnorm_f16_packed.argtypes = [vp, i32, vp, f32, vp, i32, i32, vp]
         L.ti_attn_workspace_bytes.argtypes = [i32, i32, i32, i32]
@@ -433,6 +437,13 @@ def gemm_kernel_name(bits: int, x_kind: int, M: int, N: int, K: int) -> str:
     buf = C.create_string_buffer(64)
     check(lib().ti_gemm_kernel_name(bits, x_kind, M, N, K, buf, 64))
     return buf.value.decode()
+
+
+def gemm_w8_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
+    """(rb, tpw, kwaves, grid) of the gemm_w8_kernel instance an INT8 M x N x K call launches."""
+    v = [C.c_int() for _ in range(4)]
+    check(lib().ti_gemm_w8_plan(M, N, K, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def sync() -> None:

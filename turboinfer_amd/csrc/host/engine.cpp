@@ -191,7 +191,7 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
     if ((rc = ti_memcpy_h2d(e->rope_cs, cs.data(), cs.size() * 4, e->s))) return fail(rc);
     if (const char* env = getenv("TI_ATTN_PART")) e->part_on = atoi(env) != 0;
     e->splits_max = e->splits_for(1);
-    e->pf_rows = (c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16;   // int4 (also group-32): the tile GEMM
+    e->pf_rows = chunk_rows_max(c);   // int4 (also group-32): the tile GEMM; INT8: gemm_w8_kernel
     // (affine group-32 runs the fused kernel only: prompt chunks of its 16 rows)
     e->rows_cap = std::max(B, e->pf_rows);
     const int R = e->rows_cap;
@@ -528,7 +528,7 @@ int ti_engine_prefill_attn_name(ti_engine* e, int rows, char* buf, int len) {
 }
 
 int ti_engine_set_prefill(ti_engine* e, int rows) {
-  if (!e || e->c.compat || rows < 0 || rows > e->rows_cap || (rows > 0 && rows > ((e->c.bits & ~TI_BITS_G32) == 4 ? TI_GEMM_MAX_ROWS : 16)))
+  if (!e || e->c.compat || rows < 0 || rows > e->rows_cap || (rows > 0 && rows > chunk_rows_max(e->c)))
     return ti_set_error(TI_ERR_ARG, "ti_engine_set_prefill: rows %d", rows);
   DeviceScope bind_(e);
   e->pf_rows = rows;
