@@ -278,7 +278,8 @@ int ti_gemm_packed_rows_for(int bits, int M, int N, int K);
 /* The tile GEMM's plan for an int4 (bits 4 or 4 | TI_BITS_G32) M x N x K call with a split-K
  * workspace of ws_bytes (0 = none): row-waves, weight tiles per wave and k-slices (1 = no split;
  * K is split only where one slice per column block would leave most CUs idle, TI_GEMM_SPLITK=0
- * never).  TI_ERR_UNSUPPORTED when the call would not take the tile kernel. */
+ * never).  TI_ERR_UNSUPPORTED when the call would not take the tile kernel (17..64 rows take it
+ * for wide outputs only, ti_gemm_packed_rows_for). */
 int ti_gemm_tile_plan(int bits, int M, int N, int K, int64_t ws_bytes, int* wmr, int* tpw, int* n_ks);
 /* y[m][0:K] = fp16(rms_norm(x[m][0:K]) * w), tensor_engine.cpp:1452-1508 (the batched path's
  * activation prep; the same arithmetic as the fused TI_X_F32_RMSNORM prologue). */

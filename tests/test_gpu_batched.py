@@ -213,6 +213,8 @@ def test_splitk_repeat_is_deterministic(ti, oracle, splitk_ws):
 
 @pytest.mark.parametrize("splitk", [False, True])
 def test_batched_resid_silu_logits(ti, oracle, splitk_ws, splitk):
+    """57 rows of narrow outputs: gemm_rows_kernel, which never splits K, so the splitk variant only hands the
+    workspace over and runs unsplit.  The tile kernel's epilogues, split and unsplit: test_gpu_gemm_tile.py."""
     M, K = 57, 2048
     ws = splitk_ws if splitk else None
     rng = np.random.RandomState(5)
@@ -262,6 +264,8 @@ def test_batched_resid_silu_logits(ti, oracle, splitk_ws, splitk):
 @pytest.mark.parametrize("splitk", [False, True])
 @pytest.mark.parametrize("hd,nh,nkv", [(128, 4, 4), (64, 8, 2)])
 def test_batched_qkv_rope_kv_append(ti, oracle, splitk_ws, hd, nh, nkv, splitk):
+    """45 rows: gemm_rows_kernel; its splitk variant runs unsplit too (ti_gemm_tile_plan refuses the shape).
+    QKV_ROPE_KV on the tile kernel, with a split K and both cache formats: test_gpu_gemm_tile.py."""
     M, H, max_seq, theta = 45, 512, 40, 10000.0
     qd, kvd = nh * hd, nkv * hd
     N = qd + 2 * kvd

@@ -2643,8 +2643,9 @@ extern "C" int ti_gemm_fold_partials(int bits, int M, int N, int K) {
 extern "C" int ti_gemm_tile_plan(int bits, int M, int N, int K, int64_t ws_bytes, int* wmr, int* tpw, int* n_ks) {
   const bool g32 = (bits & TI_BITS_G32) != 0;
   if (!wmr || !tpw || !n_ks) return ti_set_error(TI_ERR_ARG, "ti_gemm_tile_plan: null pointer");
-  if ((bits & ~TI_BITS_G32) != 4 || M < ti::tile_rows() || M > TI_GEMM_MAX_ROWS || N < 16 || (N & 15) || K < 128 ||
-      (K & 127))
+  // (gemm_impl's `tile`: from tile_rows() rows on, and 17..64 plain int4 rows of a wide output)
+  const bool rows_ok = M >= ti::tile_rows() || (!g32 && wide_tile(bits, M, N));
+  if ((bits & ~TI_BITS_G32) != 4 || !rows_ok || M > TI_GEMM_MAX_ROWS || N < 16 || (N & 15) || K < 128 || (K & 127))
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_tile_plan: M=%d N=%d K=%d bits %d is not a tile-kernel call", M, N,
                         K, bits);
   ti::tile_plan(M, N, K, g32, query_cus(), ti::splitk_on() ? ws_bytes : 0, wmr, tpw, n_ks);
