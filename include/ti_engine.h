@@ -99,7 +99,8 @@ int ti_engine_set_stop(ti_engine* e, int32_t token);
 /* Step-graph replays (decode steps, each covering every stream of its call) and prompt chunks
  * (prefill) this engine has run since it was created.  An INT8 (group-128) engine counts a prompt chunk
  * of R rows as ceil(R / 16): the 16-row pieces its counter has always meant, whichever kernel runs the chunk
- * (one gemm_w8_kernel launch per projection, or fused pieces with TI_GEMM_W8_ROWS=0). */
+ * (one gemm_w8_kernel launch per projection, or fused pieces with TI_GEMM_W8_ROWS=0).  A Q8_0 engine
+ * (8 | TI_BITS_G32) counts the chunks it runs, like int4: up to TI_GEMM_MAX_ROWS rows each, 16 with the knob at 0. */
 int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_chunks);
 /* The graph cache since creation: graphs captured into it (a step or verify graph the cache did not hold), and
  * graphs dropped from it (a setter or a grown buffer changed something they bake in).  Two calls between which

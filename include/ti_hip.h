@@ -103,7 +103,8 @@ int ti_wpack_host(const float* w, int K, int N_src, int N_total, int bits, int s
  * 8 weights k = 32*s4 + 8*(l >> 4) + e, so every 32-weight block is one MFMA's reduction.
  * Scales fp16 [N/16][K/128][4][16] (one per output row and 32-k block).  Runs on the fused
  * kernel (more rows than its LDS image holds: in pieces) and, int4 with fp16 rows from 65 rows
- * on, on the tile GEMM; no packed rows (ti_gemm_max_rows). */
+ * on, on the tile GEMM; int8 with aligned fp16 rows from 17 rows on, on gemm_w8_kernel's group-32
+ * instance (INT8 rows above 16, below); no packed rows (ti_gemm_max_rows). */
 #define TI_BITS_G32 32
 /* Pack exact integer weights: q int8 [K][N_src] (int4: -8..7, int8: -127..127) with fp16 block
  * scales d [K/32][N_src]: weight(k, c) = d[k/32][c] * q[k][c] exactly, as ggml dequantizes a
@@ -306,16 +307,24 @@ int ti_gemm_mb_plan(int bits, int M, int N, int K, int* grid, int* ntl);
  * any M in the range (K % 128 == 0, K <= 65535, N % 16 == 0; tiles, x and out 16-byte aligned, ldx % 8 == 0
  * and ldo % 4 == 0, else TI_ERR_UNSUPPORTED: every access of the kernel is a vector access).  The caller normalises
  * TI_X_F32_RMSNORM inputs with ti_rmsnorm_f16 first, as for int4.  Still TI_ERR_UNSUPPORTED on this route:
- * out_packed, TI_X_F16_PACKED rows, fold_x / a folded input (ss_in), and 8 | TI_BITS_G32 (Q8_0 keeps its
- * 16-row fused pieces).  ti_gemm_max_rows and ti_gemm_packed_rows[_for] are unchanged: they describe the
- * fused kernel and the int4 packed route.
- * ti_gemm_w8_rows: 1 when an M x N x K call of that kind takes gemm_w8_kernel, 0 otherwise -- also for every
- * M once the process runs with TI_GEMM_W8_ROWS=0 (read once), which restores the refusal above 16 rows.
- * ti_gemm_w8_plan: the instance such a call launches -- 16 *rb rows per workgroup (rb 2 or 4), *tpw weight
+ * out_packed, TI_X_F16_PACKED rows, fold_x / a folded input (ss_in).  ti_gemm_max_rows and
+ * ti_gemm_packed_rows[_for] are unchanged: they describe the fused kernel and the int4 packed route.
+ * 8 | TI_BITS_G32 (Q8_0 blocks) takes the kernel's group-32 instance under the same conditions (one MFMA per
+ * 32-k block from zero, acc = fmaf(block scale, block sum, acc) in k order: the fused kernel's group-32
+ * arithmetic).  Such a call never turns TI_ERR_UNSUPPORTED because of this route: where a condition fails
+ * (alignment, out_packed, a fold, another x kind, TI_GEMM_W8_ROWS=0) it runs in 16-row fused pieces as below
+ * 17 rows.
+ * ti_gemm_w8_rows_for: 1 when an M x N x K call with `bits` (8 or 8 | TI_BITS_G32) and aligned TI_X_F16 rows
+ * takes gemm_w8_kernel, 0 otherwise -- also for every M once the process runs with TI_GEMM_W8_ROWS=0 (read
+ * once), which restores the refusal (group 128) or the fused pieces (group 32) above 16 rows.
+ * ti_gemm_w8_plan_for: the instance such a call launches -- 16 *rb rows per workgroup (rb 2 or 4), *tpw weight
  * tiles per wave, *kwaves k-waves (8 / *kwaves column-waves; K is split inside the workgroup only, summed in
- * k-wave order) and *grid workgroups.  TI_ERR_UNSUPPORTED when ti_gemm_w8_rows is 0. */
+ * k-wave order) and *grid workgroups.  TI_ERR_UNSUPPORTED when ti_gemm_w8_rows_for is 0.
+ * ti_gemm_w8_rows / ti_gemm_w8_plan: the bits == 8 forms. */
 int ti_gemm_w8_rows(int M, int N, int K);
 int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
+int ti_gemm_w8_rows_for(int bits, int M, int N, int K);
+int ti_gemm_w8_plan_for(int bits, int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

@@ -171,7 +171,7 @@ EXPORTED = [
     "ti_sample_step_rows", "ti_sample_device_rows", "ti_penalty_step_rows", "ti_engine_serve_requests",
     "ti_guide_step_rows", "ti_engine_add_guide", "ti_engine_remove_guide", "ti_engine_guide_count",
     "ti_engine_serve_requests_guided", "ti_engine_graph_counters",
-    "ti_gemm_w8_rows", "ti_gemm_w8_plan",
+    "ti_gemm_w8_rows", "ti_gemm_w8_plan", "ti_gemm_w8_rows_for", "ti_gemm_w8_plan_for",
 ]
 
 _lib = None
@@ -220,6 +220,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_gemm_w8_rows"):   # (older TI_LIB builds in A/B runs lack the INT8 rows kernel)
             L.ti_gemm_w8_rows.argtypes = [i32, i32, i32]
             L.ti_gemm_w8_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
+        if hasattr(L, "ti_gemm_w8_rows_for"):   # (older TI_LIB builds in A/B runs lack the group-32 instance)
+            L.ti_gemm_w8_rows_for.argtypes = [i32, i32, i32, i32]
+            L.ti_gemm_w8_plan_for.argtypes = [i32, i32, i32, i32] + [C.POINTER(C.c_int)] * 4
         L.ti_rmsnorm_f16.argtypes = [vp, i32, vp, f32, vp, i32, i32, i32, vp]
         L.ti_rmsnorm_f16_packed.argtypes = [vp, i32, vp, f32, vp, i32, i32, vp]
         L.ti_attn_workspace_bytes.argtypes = [i32, i32, i32, i32]
@@ -439,10 +442,14 @@ def gemm_kernel_name(bits: int, x_kind: int, M: int, N: int, K: int) -> str:
     return buf.value.decode()
 
 
-def gemm_w8_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
-    """(rb, tpw, kwaves, grid) of the gemm_w8_kernel instance an INT8 M x N x K call launches."""
+def gemm_w8_plan(M: int, N: int, K: int, bits: int = 8) -> tuple[int, int, int, int]:
+    """(rb, tpw, kwaves, grid) of the gemm_w8_kernel instance an INT8 (bits 8, or 8 | BITS_G32 for Q8_0
+    blocks) M x N x K call launches."""
     v = [C.c_int() for _ in range(4)]
-    check(lib().ti_gemm_w8_plan(M, N, K, *[C.byref(x) for x in v]))
+    if bits == 8:
+        check(lib().ti_gemm_w8_plan(M, N, K, *[C.byref(x) for x in v]))
+    else:
+        check(lib().ti_gemm_w8_plan_for(bits, M, N, K, *[C.byref(x) for x in v]))
     return tuple(x.value for x in v)
 
 

@@ -125,9 +125,10 @@ __device__ __forceinline__ int tile_swz(int row) { return TI_TILE_SWZ4 ? (row + 
 // (8 / kw column-waves), n_cb column blocks x n_rb row blocks in `grid` workgroups, `lds` bytes of LDS.
 struct W8Plan {
   int rb, tpw, kw, n_cb, n_rb, grid, lds;
+  bool g32;   // the group-32 instance (Q8_0 blocks, 8 | TI_BITS_G32)
 };
 bool w8_rows_on();   // TI_GEMM_W8_ROWS (0: the route is off)
-W8Plan w8_plan(int M, int N, int K, int cus);
+W8Plan w8_plan(int M, int N, int K, int cus, bool g32 = false);
 int w8_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
 int launch_w8(const GemvArgs& a, const W8Plan& p, hipStream_t s);
 

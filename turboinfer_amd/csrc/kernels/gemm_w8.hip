@@ -1,6 +1,7 @@
-// gemm_w8.hip -- INT8 group-128 weights x fp16 rows on MFMA for 17 .. TI_GEMM_MAX_ROWS rows (gfx950):
-// batched decode above 16 streams and prompt chunks of INT8 engines (ti_gemm_wq_a16 with bits 8, TI_X_F16
-// rows, M >= 17).  The fused gemv_wq_kernel stays the INT8 kernel up to 16 rows.
+// gemm_w8.hip -- INT8 weights (group-128, and group-32 Q8_0 blocks) x fp16 rows on MFMA for 17 ..
+// TI_GEMM_MAX_ROWS rows (gfx950): batched decode above 16 streams and prompt chunks of INT8 engines
+// (ti_gemm_wq_a16 with bits 8 or 8 | TI_BITS_G32, TI_X_F16 rows, M >= 17).  The fused
+// gemv_wq_kernel stays the INT8 kernel up to 16 rows.  Group-128 first:
 //
 // y[M][N] = x[M][K] . W with W in the INT8 tiles and fp16 group scales of ti_wpack_host(.., 8): a tile is
 // 16 outputs x 128 k (2 KiB, two 1 KiB chunks; lane l of chunk c: 16 bytes of output l & 15 from
@@ -23,6 +24,12 @@
 //     the result is bit-reproducible: no split-K between workgroups, no tickets, no atomics on the sums);
 //     the column-waves of k-wave 0 run the staged epilogue (tile_epilogue_lds; STORE_F16 and
 //     LOGITS_ARGMAX are staged the same way here).
+//
+// G32 instances (bits 8 | TI_BITS_G32, GGUF Q8_0 blocks): the same work split on group-32 tiles
+// (lane l's bytes 8 s4 .. + 7 are k = 32 s4 + 8 (l >> 4) .. + 7, scales [N/16][K/128][4][16]).  One MFMA from
+// zero sums one 32-k block and acc = fmaf(block scale, block sum, acc) runs per block in k order, the fused
+// kernel's group-32 arithmetic.  The 64 scales of a tile and group ride in the ring as one coalesced 2-byte
+// load per lane; a ds_bpermute per block hands lane (r, kq) the scale of (block, output r).  See compute32.
 #include <stdlib.h>
 
 #include "gemm_shared.hpp"
@@ -64,7 +71,7 @@ __host__ __device__ constexpr int w8_lds_bytes(int rb, int kw) {
   return w8_x_bytes(rb, kw) > tile_epi_lds_bytes() ? w8_x_bytes(rb, kw) : tile_epi_lds_bytes();
 }
 
-template <int RB, int TPW, int KW>
+template <int RB, int TPW, int KW, bool G32 = false>
 __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs a, int n_cb, int n_rb) {
   const unsigned long long t_entry = stamp_now();
   constexpr int WC = kGemvWaves / KW, BM = 16 * RB;   // column-waves, rows per workgroup
@@ -110,7 +117,8 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
   for (int t = 0; t < TPW; ++t) {
     const int tn = min(t0 + wn * TPW + t, NT - 1);
     wt[t] = a.tiles + (size_t)tn * KT * (2 * kWave) + lane;
-    st[t] = a.scales + (size_t)tn * KT * 16 + r;
+    // group-32: the 64 scales of a tile and group are [block s4][output], lane l loads entry l
+    st[t] = a.scales + (size_t)tn * KT * (G32 ? 64 : 16) + (G32 ? lane : r);
   }
   u32x4 W[D][TPW][2];
   uint16_t S[D][TPW];
@@ -120,7 +128,7 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
     for (int t = 0; t < TPW; ++t) {
       W[slot][t][0] = wt[t][(size_t)kg * (2 * kWave)];
       W[slot][t][1] = wt[t][(size_t)kg * (2 * kWave) + kWave];
-      S[slot][t] = st[t][kg * 16];
+      S[slot][t] = st[t][kg * (G32 ? 64 : 16)];
     }
   };
 
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
 
   // lane (r, kq): A fragment s4 of row block b = row b 16 + r, k = 32 kq + 8 s4 .. + 7 (chunk 4 kq + s4);
   // B fragment s4 = the lane's bytes 8 s4 .. + 7 of the tile row r, the same k
-  auto compute = [&](int slot, int j) __attribute__((always_inline)) {
+  auto compute128 = [&](int slot, int j) __attribute__((always_inline)) {
     const f16* xrow = xb + (j & 1) * (KW * BM * 128) + (q * BM + r) * 128;
     f32x4 tmp[TPW][RB];
 #pragma unroll
@@ -159,6 +167,47 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[t][b][i] = fmaf(sc, tmp[t][b][i], acc[t][b][i]);
     }
+  };
+
+  // Group-32 tiles (Q8_0 blocks): the lane's bytes 8 s4 .. + 7 are k = 32 s4 + 8 kq .. + 7, so the A fragment
+  // of step s4 is chunk 4 s4 + kq and one MFMA from zero is one block's sum; acc = fmaf(scale(block s4,
+  // output r), sum, acc) for s4 = 0 .. 3 in that order (gemv_body<8, .., G32>).  Lane 16 s4 + r loaded that
+  // scale (load_w): one ds_bpermute per block and tile hands it to the four lanes (r, kq).  The TPW x 4
+  // (block, tile) units run as one software pipeline, the MFMAs of unit u + 1 ahead of the FMAs of unit
+  // u, so only two units' sums (2 RB f32x4) are live beside the accumulators.
+  auto compute32 = [&](int slot, int j) __attribute__((always_inline)) {
+    const f16* xrow = xb + (j & 1) * (KW * BM * 128) + (q * BM + r) * 128;
+    constexpr int NU = 4 * TPW;   // unit u: block s4 = u / TPW of tile t = u % TPW
+    float sc[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      sc[u] = h2f((uint16_t)__builtin_amdgcn_ds_bpermute(4 * (16 * (u / TPW) + r), (int)S[slot][u % TPW]));
+    f16x8 xf[RB];
+    f32x4 sum[2][RB];
+    auto mfmas = [&](int u) __attribute__((always_inline)) {
+      const int s4 = u / TPW, t = u % TPW;
+      if (t == 0) {
+#pragma unroll
+        for (int b = 0; b < RB; ++b) xf[b] = *(const f16x8*)(xrow + b * 16 * 128 + (((s4 * 4 + kq) ^ tile_swz(r)) * 8));
+      }
+      const f16x8 bf = dequant_step<8>(W[slot][t], s4, 0u);
+#pragma unroll
+      for (int b = 0; b < RB; ++b)
+        sum[u & 1][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[b], bf, (f32x4){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+    };
+    mfmas(0);
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      if (u + 1 < NU) mfmas(u + 1);
+#pragma unroll
+      for (int b = 0; b < RB; ++b)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[u % TPW][b][i] = fmaf(sc[u], sum[u & 1][b][i], acc[u % TPW][b][i]);
+    }
+  };
+  auto compute = [&](int slot, int j) __attribute__((always_inline)) {
+    if constexpr (G32) compute32(slot, j);
+    else compute128(slot, j);
   };
 
   // ---- the stream.  Step j: x(j + 1) -> registers, W(j + D - 1) -> ring (x first: the wait for x at the
@@ -250,8 +299,9 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// TI_GEMM_W8_ROWS=0: INT8 rows above 16 are refused by ti_gemm_wq_a16 and cut into 16-row fused pieces by the
-// engine, as before this kernel (A/B knob, read once per process).
+// TI_GEMM_W8_ROWS=0: INT8 rows above 16 are refused by ti_gemm_wq_a16 (group-32: cut into 16-row fused pieces
+// there) and cut into 16-row fused pieces by the engine, as before this kernel (A/B knob, read once per
+// process).
 bool w8_rows_on() {
   static const bool on = [] {
     const char* e = getenv("TI_GEMM_W8_ROWS");
@@ -260,32 +310,38 @@ bool w8_rows_on() {
   return on;
 }
 
-#define TI_W8_FNS_RB(RB)                                                                                       \
-  (const void*)gemm_w8_kernel<RB, 1, 1>, (const void*)gemm_w8_kernel<RB, 1, 2>, (const void*)gemm_w8_kernel<RB, 1, 4>, \
-      (const void*)gemm_w8_kernel<RB, 2, 1>, (const void*)gemm_w8_kernel<RB, 2, 2>, (const void*)gemm_w8_kernel<RB, 2, 4>
-static const void* const g_w8_fns[] = {TI_W8_FNS_RB(2), TI_W8_FNS_RB(4), (const void*)gemm_w8_kernel<2, 1, 8>,
-                                       (const void*)gemm_w8_kernel<2, 2, 8>};
-static const void* w8_fn(int rb, int tpw, int kw) {
-  if (kw == 8) return g_w8_fns[12 + tpw - 1];
-  return g_w8_fns[(rb == 4 ? 6 : 0) + (tpw - 1) * 3 + (kw == 1 ? 0 : kw == 2 ? 1 : 2)];
+#define TI_W8_FNS_RB(RB, G)                                                                           \
+  (const void*)gemm_w8_kernel<RB, 1, 1, G>, (const void*)gemm_w8_kernel<RB, 1, 2, G>,                  \
+      (const void*)gemm_w8_kernel<RB, 1, 4, G>, (const void*)gemm_w8_kernel<RB, 2, 1, G>,              \
+      (const void*)gemm_w8_kernel<RB, 2, 2, G>, (const void*)gemm_w8_kernel<RB, 2, 4, G>
+#define TI_W8_FNS(G)                                                                        \
+  TI_W8_FNS_RB(2, G), TI_W8_FNS_RB(4, G), (const void*)gemm_w8_kernel<2, 1, 8, G>,          \
+      (const void*)gemm_w8_kernel<2, 2, 8, G>
+static const void* const g_w8_fns[] = {TI_W8_FNS(false), TI_W8_FNS(true)};   // 14 group-128, 14 group-32
+static const void* w8_fn(int rb, int tpw, int kw, bool g32) {
+  const int i = kw == 8 ? 12 + tpw - 1 : (rb == 4 ? 6 : 0) + (tpw - 1) * 3 + (kw == 1 ? 0 : kw == 2 ? 1 : 2);
+  return g_w8_fns[(g32 ? 14 : 0) + i];
 }
 
 // The plan, by a per-CU byte model (as tile_shape): RB 2 up to 32 rows, else 4; over tiles per wave TPW in
 // {1, 2} and k-waves KW in {1, 2, 4, 8 (RB 2)} with KW <= K / 128, the launch takes
 // ceil(workgroups of an XCD / its CUs) rounds, a workgroup moves per 128-k group its x rows (16 RB x 256 B)
-// and its (8 / KW) TPW tiles of 2 KiB, and a k-wave split adds its slabs' trip through LDS once; the
-// cheapest shape wins, ties to fewer k-waves and then to more tiles per wave.
-W8Plan w8_plan(int M, int N, int K, int cus) {
+// and its (8 / KW) TPW tiles of 2 KiB (group-32: + 128 B of block scales each), and a k-wave split adds its
+// slabs' trip through LDS once; the cheapest shape wins, ties to fewer k-waves and then to more tiles per
+// wave.  Every (RB, TPW, KW) is a candidate for both group sizes: no group-32 instance uses scratch.
+W8Plan w8_plan(int M, int N, int K, int cus, bool g32) {
   const int NT = N >> 4, KT = K >> 7, rb = M <= 32 ? 2 : 4, bm = 16 * rb;
   const int n_rb = (M + bm - 1) / bm, xcd_cus = cus >= 8 ? cus / 8 : 1;
+  const int tile_bytes = 2048 + (g32 ? 128 : 0);   // (the 32 B of group-128 scales were never counted)
   W8Plan best{};
+  best.g32 = g32;
   long best_cost = -1;
   for (int kw : {1, 2, 4, 8}) {
     if (kw > KT || rb * kw > 16) continue;
     for (int tpw : {2, 1}) {
       const int cols = (8 / kw) * tpw, n_cb = (NT + cols - 1) / cols;
       const long per_xcd = (long)(n_cb + 7) / 8 * n_rb, rounds = (per_xcd + xcd_cus - 1) / xcd_cus;
-      const long cost = rounds * ((long)KT * (bm * 256 + cols * 2048) + (kw > 1 ? (long)(kw - 1) * cols * rb * 1024 : 0));
+      const long cost = rounds * ((long)KT * (bm * 256 + cols * tile_bytes) + (kw > 1 ? (long)(kw - 1) * cols * rb * 1024 : 0));
       if (best_cost < 0 || cost < best_cost) {
         best_cost = cost;
         best.rb = rb; best.tpw = tpw; best.kw = kw; best.n_cb = n_cb; best.n_rb = n_rb;
@@ -308,7 +364,7 @@ int launch_w8(const GemvArgs& a, const W8Plan& p, hipStream_t s) {
   GemvArgs args = a;
   int n_cb = p.n_cb, n_rb = p.n_rb;
   void* kargs[] = {&args, &n_cb, &n_rb};
-  TI_HIP_CHECK(hipLaunchKernel(w8_fn(p.rb, p.tpw, p.kw), dim3(p.grid), dim3(kGemvThreads), kargs, p.lds, s),
+  TI_HIP_CHECK(hipLaunchKernel(w8_fn(p.rb, p.tpw, p.kw, p.g32),dim3(p.grid), dim3(kGemvThreads), kargs, p.lds, s),
                "hipLaunchKernel(gemm_w8_kernel)");
   TI_LAUNCH_CHECK("gemm_w8_kernel");
   return TI_OK;

@@ -2608,23 +2608,29 @@ static bool wide_tile(int bits, int M, int N) {
   if (M <= 32 && ti::tile_rb2_on() && N >= kWideN32) return true;
   return (long)M * N >= kWideMN;
 }
-// INT8 (group-128) fp16 rows above 16: gemm_w8_kernel (gemm_w8.hip); TI_GEMM_W8_ROWS=0 turns the route off.
+// INT8 fp16 rows above 16, group-128 (bits 8) or group-32 (8 | TI_BITS_G32, Q8_0 blocks): gemm_w8_kernel
+// (gemm_w8.hip); TI_GEMM_W8_ROWS=0 turns the route off for both.
 static bool w8_route(int bits, int x_kind, int M) {
-  return bits == 8 && x_kind == TI_X_F16 && M > 16 && M <= TI_GEMM_MAX_ROWS && ti::w8_rows_on();
+  return (bits & ~TI_BITS_G32) == 8 && x_kind == TI_X_F16 && M > 16 && M <= TI_GEMM_MAX_ROWS && ti::w8_rows_on();
 }
-extern "C" int ti_gemm_w8_rows(int M, int N, int K) {
-  return w8_route(8, TI_X_F16, M) && N >= 16 && !(N & 15) && K >= 128 && !(K & 127) && K <= 0xffff ? 1 : 0;
+extern "C" int ti_gemm_w8_rows_for(int bits, int M, int N, int K) {
+  return w8_route(bits, TI_X_F16, M) && N >= 16 && !(N & 15) && K >= 128 && !(K & 127) && K <= 0xffff ? 1 : 0;
 }
-extern "C" int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
+extern "C" int ti_gemm_w8_rows(int M, int N, int K) { return ti_gemm_w8_rows_for(8, M, N, K); }
+extern "C" int ti_gemm_w8_plan_for(int bits, int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
   if (!rb || !tpw || !kwaves || !grid) return ti_set_error(TI_ERR_ARG, "ti_gemm_w8_plan: null pointer");
-  if (!ti_gemm_w8_rows(M, N, K))
-    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_w8_plan: M=%d N=%d K=%d is not a gemm_w8_kernel call", M, N, K);
-  const ti::W8Plan p = ti::w8_plan(M, N, K, query_cus());
+  if (!ti_gemm_w8_rows_for(bits, M, N, K))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_w8_plan: bits %d M=%d N=%d K=%d is not a gemm_w8_kernel call", bits,
+                        M, N, K);
+  const ti::W8Plan p = ti::w8_plan(M, N, K, query_cus(), (bits & TI_BITS_G32) != 0);
   *rb = p.rb;
   *tpw = p.tpw;
   *kwaves = p.kw;
   *grid = p.grid;
   return TI_OK;
+}
+extern "C" int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
+  return ti_gemm_w8_plan_for(8, M, N, K, rb, tpw, kwaves, grid);
 }
 extern "C" int ti_gemm_packed_rows(int bits, int M) { return bits == 4 && M > 16 && M < ti::tile_rows() ? 1 : 0; }
 extern "C" int ti_gemm_packed_rows_for(int bits, int M, int N, int K) {
@@ -2767,7 +2773,13 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     default:
       return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: unknown epilogue %d", epi->kind);
   }
-  if (g32 && !g32_tile && !g32_rowsk && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
+  // every access of gemm_w8_kernel is a vector access: 16-byte weight, x and output pieces
+  const bool w8_vec = !((((uintptr_t)tiles | (uintptr_t)x | (uintptr_t)epi->out) & 15) || ((uintptr_t)scales & 1) ||
+                        (ldx & 7) || (epi->ldo & 3));
+  // group-32 INT8 (Q8_0) fp16 rows above 16: the kernel's group-32 instance where it can serve the call,
+  // else (unlike group-128 INT8, which has nothing else there) the fused pieces below
+  const bool g32_w8 = g32 && w8_route(bits, x_kind, M) && w8_vec && !epi->out_packed && !fold_out && !fold_in;
+  if (g32 && !g32_tile && !g32_rowsk && !g32_w8 && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
     if (x_kind == TI_X_ATTN_SPLITS || x_kind == TI_X_F16_FOLDED || epi->out_packed)
       return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: group-32 rows > 16 need plain x rows");
     const size_t x_elem = x_kind == TI_X_F16 ? 2 : 4;
@@ -2789,15 +2801,14 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     }
     return TI_OK;
   }
-  if (!g32 && w8_route(bits, x_kind, M)) {   // INT8 rows above 16: gemm_w8_kernel
+  if (g32 ? g32_w8 : w8_route(bits, x_kind, M)) {   // INT8 rows above 16: gemm_w8_kernel
     if (epi->out_packed || fold_out || fold_in)
       return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: INT8 rows above 16 take row-major fp16 x and outputs, "
                           "no fold (M=%d)", M);
-    // every access of the kernel is a vector access: 16-byte weight, x and output pieces
-    if ((((uintptr_t)tiles | (uintptr_t)x | (uintptr_t)epi->out) & 15) || ((uintptr_t)scales & 1) || (ldx & 7) || (epi->ldo & 3))
+    if (!w8_vec)
       return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: INT8 rows above 16 need 16-byte aligned tiles, x and out, "
                           "ldx %% 8 == 0 and ldo %% 4 == 0 (ldx=%d ldo=%d)", ldx, epi->ldo);
-    const W8Plan p = w8_plan(M, N, K, query_cus());
+    const W8Plan p = w8_plan(M, N, K, query_cus(), g32);
     if (p.lds > 64 * 1024) {   // no-op once this device is prepared
       const int rc = ti_gemm_prepare();
       if (rc != TI_OK) return rc;
@@ -2899,15 +2910,21 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
 
 extern "C" int ti_epilogue_bytes(void) { return (int)sizeof(ti_epilogue); }
 
-// The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights: the same predicates as
-// gemm_impl (use_batched, wide_tile, tile_rows, rows_on).  For bench / profile labels.
+// The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights and for 8 | TI_BITS_G32 (aligned
+// row-major calls): the same predicates as gemm_impl (use_batched, wide_tile, tile_rows, rows_on, w8_route).
+// For bench / profile labels.
 extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len) {
   using namespace ti;
+  const bool q8_0 = bits == (8 | TI_BITS_G32);
   if (!buf || len < 1) return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: null buffer");
-  if ((bits != 4 && bits != 8 && bits != 16) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
+  if ((bits != 4 && bits != 8 && bits != 16 && !q8_0) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
     return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: bits %d M %d N %d K %d", bits, M, N, K);
   if (w8_route(bits, x_kind, M)) {
     snprintf(buf, (size_t)len, "gemm_w8_kernel");
+    return TI_OK;
+  }
+  if (q8_0) {   // the fused kernel, more than 16 rows in pieces
+    snprintf(buf, (size_t)len, "gemv_wq_kernel<8,%d>", gemv_xmode(x_kind, M, K));
     return TI_OK;
   }
   const bool packed_x = x_kind == TI_X_F16_PACKED;
