@@ -41,6 +41,11 @@ $(BUILD)/k_gemm_w8.o: turboinfer_amd/csrc/kernels/gemm_w8.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
+# gemm_w16: the flags of gemm_w8 (its k-wave sums and epilogues are the same code)
+$(BUILD)/k_gemm_w16.o: turboinfer_amd/csrc/kernels/gemm_w16.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
 $(BUILD)/k_attention.o: turboinfer_amd/csrc/kernels/attention.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@

@@ -266,7 +266,9 @@ int ti_gemm_lds_bytes(int M, int N, int K);
  * TI_GEMM_MAX_ROWS rows at any K (batched decode, generate_batch inference_engine.cpp:804-828)
  * and is used above 2 rows (a fixed crossover).  An int4 caller with more rows
  * than this returns for TI_X_F32_RMSNORM should normalise them with ti_rmsnorm_f16 and pass
- * TI_X_F16 rows.  0 = shape unsupported. */
+ * TI_X_F16 rows.  bits 8 and 16 report the fused kernel's rows here although aligned TI_X_F16 calls of
+ * 17 .. TI_GEMM_MAX_ROWS rows run on gemm_w8_kernel / gemm_w16_kernel (ti_gemm_w8_rows_for, ti_gemm_w16_rows,
+ * below).  0 = shape unsupported. */
 #define TI_GEMM_MAX_ROWS 1024
 int ti_gemm_max_rows(int bits, int x_kind, int N, int K);
 /* 1 when M rows of an int4 GEMM go to the batched-rows kernel (17 .. 64 rows): its fp16
@@ -325,6 +327,22 @@ int ti_gemm_w8_rows(int M, int N, int K);
 int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 int ti_gemm_w8_rows_for(int bits, int M, int N, int K);
 int ti_gemm_w8_plan_for(int bits, int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
+/* fp16 weights above 16 rows.  ti_gemm_wq_a16 with bits 16, TI_X_F16 rows and 17 <= M <= TI_GEMM_MAX_ROWS runs
+ * gemm_w16_kernel: one launch, the fused kernel's fp16 arithmetic (one fp32 accumulator threaded through the
+ * MFMAs of a k-wave's groups; the k-waves summed in fixed order, so a second launch gives the same bits), every
+ * epilogue kind, any M in the range, under gemm_w8_kernel's conditions (K % 128 == 0, K <= 65535, N % 16 == 0;
+ * tiles, x and out 16-byte aligned, ldx % 8 == 0 and ldo % 4 == 0).  `scales` is not read (may be NULL).
+ * TI_ERR_UNSUPPORTED on this route, since no other kernel serves fp16 weights above 16 rows: unaligned
+ * operands, out_packed, fold_x / a folded input (ss_in); TI_X_F16_PACKED rows stay int4-only.
+ * ti_gemm_max_rows(16, ..) and ti_gemm_packed_rows[_for] are unchanged: they describe the fused kernel and the
+ * int4 packed route.
+ * ti_gemm_w16_rows: 1 when an M x N x K call with bits 16 and aligned TI_X_F16 rows takes gemm_w16_kernel, 0
+ * otherwise -- also for every M once the process runs with TI_GEMM_W16_ROWS=0 (read once), which restores the
+ * refusal above 16 rows (engines then cut rows into 16-row fused pieces).
+ * ti_gemm_w16_plan: the instance such a call launches, in ti_gemm_w8_plan's terms (*rb 2 or 4).
+ * TI_ERR_UNSUPPORTED when ti_gemm_w16_rows is 0. */
+int ti_gemm_w16_rows(int M, int N, int K);
+int ti_gemm_w16_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

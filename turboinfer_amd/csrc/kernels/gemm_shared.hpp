@@ -1,5 +1,5 @@
-// gemm_shared.hpp -- what the GEMM kernels of gemv.hip (int4 tile kernel) and gemm_w8.hip (INT8 rows
-// kernel) have in common and is independent of the weight format: the launch arguments, the swizzled
+// gemm_shared.hpp -- what the GEMM kernels of gemv.hip (int4 tile kernel), gemm_w8.hip (INT8 rows
+// kernel) and gemm_w16.hip (fp16-weight rows kernel) have in common and is independent of the weight format: the launch arguments, the swizzled
 // activation image in LDS, the staged epilogue of a 64 x 16 output block.
 #pragma once
 #include "common.hpp"
@@ -107,6 +107,35 @@ __device__ __forceinline__ void tile_epilogue_lds(const GemvArgs& a, int tn, int
   }
 }
 
+// STORE_F16 and LOGITS_ARGMAX of weight tile tn from the wave's staging block (the layout of
+// tile_epilogue_lds: lane l owns columns 4 (l & 3) .. + 3 of rows 16 it + l / 4).  best[it]: the lane's
+// running argmax key of its rows (epilogue_mb's keys: the value's order key above, the lowest index wins).
+template <int RB>
+__device__ __forceinline__ void tile_epilogue_extra(const GemvArgs& a, int tn, int mb, const float* stg, int lane,
+                                                    unsigned long long (&best)[RB]) {
+  const ti_epilogue& e = a.epi;
+  const int c4 = 4 * (lane & 3), ng = tn * 16 + c4;
+#pragma unroll
+  for (int it = 0; it < RB; ++it) {
+    const int row = 16 * it + (lane >> 2), m = mb + row;
+    const float4 v = *(const float4*)(stg + row * kTileEpiStride + c4);
+    if (m >= a.M) continue;
+    if (e.kind == TI_EPI_STORE_F16) {
+      *(uint2*)((uint16_t*)e.out + (size_t)m * e.ldo + ng) =
+          make_uint2(f2h(v.x) | ((uint32_t)f2h(v.y) << 16), f2h(v.z) | ((uint32_t)f2h(v.w) << 16));
+    } else {   // TI_EPI_LOGITS_ARGMAX
+      *(float4*)((float*)e.out + (size_t)m * e.ldo + ng) = v;
+      const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned long long key = ((unsigned long long)float_order_key(vv[j]) << 32) |
+                                       (unsigned long long)(0xFFFFFFFFu - (uint32_t)(ng + j));
+        best[it] = key > best[it] ? key : best[it];
+      }
+    }
+  }
+}
+
 // Physical 16-byte chunk of logical chunk c in activation row `row` of the tile kernel's LDS image:
 // c ^ tile_swz(row).  An A-fragment read (ds_read_b128, lane l: row l & 15, chunk 4 (l >> 4) + s, or
 // 4 s + (l >> 4) with group-32 weights) is serviced in the lane groups {0-3,12-15,20-27},
@@ -131,5 +160,15 @@ bool w8_rows_on();   // TI_GEMM_W8_ROWS (0: the route is off)
 W8Plan w8_plan(int M, int N, int K, int cus, bool g32 = false);
 int w8_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
 int launch_w8(const GemvArgs& a, const W8Plan& p, hipStream_t s);
+
+// ------------------------------------------------------------ gemm_w16.hip (fp16-weight rows kernel), host side
+// The instance of gemm_w16_kernel a call takes, in W8Plan's terms.
+struct W16Plan {
+  int rb, tpw, kw, n_cb, n_rb, grid, lds;
+};
+bool w16_rows_on();   // TI_GEMM_W16_ROWS (0: the route is off)
+W16Plan w16_plan(int M, int N, int K, int cus);
+int w16_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
+int launch_w16(const GemvArgs& a, const W16Plan& p, hipStream_t s);
 
 }  // namespace ti

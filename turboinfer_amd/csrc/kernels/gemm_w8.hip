@@ -36,35 +36,6 @@
 
 namespace ti {
 
-// STORE_F16 and LOGITS_ARGMAX of weight tile tn from the wave's staging block (the layout of
-// tile_epilogue_lds: lane l owns columns 4 (l & 3) .. + 3 of rows 16 it + l / 4).  best[it]: the lane's
-// running argmax key of its rows (epilogue_mb's keys: the value's order key above, the lowest index wins).
-template <int RB>
-__device__ __forceinline__ void w8_epilogue_extra(const GemvArgs& a, int tn, int mb, const float* stg, int lane,
-                                                  unsigned long long (&best)[RB]) {
-  const ti_epilogue& e = a.epi;
-  const int c4 = 4 * (lane & 3), ng = tn * 16 + c4;
-#pragma unroll
-  for (int it = 0; it < RB; ++it) {
-    const int row = 16 * it + (lane >> 2), m = mb + row;
-    const float4 v = *(const float4*)(stg + row * kTileEpiStride + c4);
-    if (m >= a.M) continue;
-    if (e.kind == TI_EPI_STORE_F16) {
-      *(uint2*)((uint16_t*)e.out + (size_t)m * e.ldo + ng) =
-          make_uint2(f2h(v.x) | ((uint32_t)f2h(v.y) << 16), f2h(v.z) | ((uint32_t)f2h(v.w) << 16));
-    } else {   // TI_EPI_LOGITS_ARGMAX
-      *(float4*)((float*)e.out + (size_t)m * e.ldo + ng) = v;
-      const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned long long key = ((unsigned long long)float_order_key(vv[j]) << 32) |
-                                       (unsigned long long)(0xFFFFFFFFu - (uint32_t)(ng + j));
-        best[it] = key > best[it] ? key : best[it];
-      }
-    }
-  }
-}
-
 constexpr int w8_ring(int tpw) { return tpw == 1 ? 4 : 3; }   // weight ring depth (steps)
 __host__ __device__ constexpr int w8_x_bytes(int rb, int kw) { return 2 * kw * 16 * rb * 256; }
 __host__ __device__ constexpr int w8_lds_bytes(int rb, int kw) {
@@ -274,7 +245,7 @@ __global__ __launch_bounds__(kGemvThreads, 1) void gemm_w8_kernel(const GemvArgs
 #pragma unroll
         for (int i = 0; i < 4; ++i) stg[(b * 16 + 4 * kq + i) * kTileEpiStride + r] = acc[t][b][i];
       if (tn < NT) {
-        if (extra) w8_epilogue_extra<RB>(a, tn, m0, stg, lane, best);
+        if (extra) tile_epilogue_extra<RB>(a, tn, m0, stg, lane, best);
         else tile_epilogue_lds<RB>(a, tn, m0, stg, lane);
       }
     }

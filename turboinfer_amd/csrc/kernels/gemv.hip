@@ -2568,6 +2568,7 @@ extern "C" int ti_gemm_prepare(void) {
     TI_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
                  "hipFuncSetAttribute(gemv_wq_kernel)");
   if (const int rc = w8_prepare()) return rc;
+  if (const int rc = w16_prepare()) return rc;
   g_prepared.fetch_or(bit, std::memory_order_acq_rel);
   return TI_OK;
 }
@@ -2631,6 +2632,24 @@ extern "C" int ti_gemm_w8_plan_for(int bits, int M, int N, int K, int* rb, int* 
 }
 extern "C" int ti_gemm_w8_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
   return ti_gemm_w8_plan_for(8, M, N, K, rb, tpw, kwaves, grid);
+}
+// fp16-weight fp16 rows above 16: gemm_w16_kernel (gemm_w16.hip); TI_GEMM_W16_ROWS=0 turns the route off.
+static bool w16_route(int bits, int x_kind, int M) {
+  return bits == 16 && x_kind == TI_X_F16 && M > 16 && M <= TI_GEMM_MAX_ROWS && ti::w16_rows_on();
+}
+extern "C" int ti_gemm_w16_rows(int M, int N, int K) {
+  return w16_route(16, TI_X_F16, M) && N >= 16 && !(N & 15) && K >= 128 && !(K & 127) && K <= 0xffff ? 1 : 0;
+}
+extern "C" int ti_gemm_w16_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
+  if (!rb || !tpw || !kwaves || !grid) return ti_set_error(TI_ERR_ARG, "ti_gemm_w16_plan: null pointer");
+  if (!ti_gemm_w16_rows(M, N, K))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_w16_plan: M=%d N=%d K=%d is not a gemm_w16_kernel call", M, N, K);
+  const ti::W16Plan p = ti::w16_plan(M, N, K, query_cus());
+  *rb = p.rb;
+  *tpw = p.tpw;
+  *kwaves = p.kw;
+  *grid = p.grid;
+  return TI_OK;
 }
 extern "C" int ti_gemm_packed_rows(int bits, int M) { return bits == 4 && M > 16 && M < ti::tile_rows() ? 1 : 0; }
 extern "C" int ti_gemm_packed_rows_for(int bits, int M, int N, int K) {
@@ -2828,6 +2847,34 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
     return launch_w8(a, p, (hipStream_t)stream);
   }
+  if (!g32 && w16_route(bits, x_kind, M)) {   // fp16-weight rows above 16: gemm_w16_kernel (nothing else serves them)
+    if (epi->out_packed || fold_out || fold_in)
+      return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: fp16-weight rows above 16 take row-major fp16 x and "
+                          "outputs, no fold (M=%d)", M);
+    // every access of the kernel is a vector access, as in gemm_w8_kernel (scales are not read: any pointer)
+    if ((((uintptr_t)tiles | (uintptr_t)x | (uintptr_t)epi->out) & 15) || (ldx & 7) || (epi->ldo & 3))
+      return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: fp16-weight rows above 16 need 16-byte aligned tiles, x "
+                          "and out, ldx %% 8 == 0 and ldo %% 4 == 0 (ldx=%d ldo=%d)", ldx, epi->ldo);
+    const W16Plan p = w16_plan(M, N, K, query_cus());
+    if (p.lds > 64 * 1024) {   // no-op once this device is prepared
+      const int rc = ti_gemm_prepare();
+      if (rc != TI_OK) return rc;
+    }
+    GemvArgs a;
+    a.tiles = (const u32x4*)tiles;
+    a.scales = nullptr;
+    a.x = x;
+    a.norm_w = norm_w;
+    a.eps = eps;
+    a.x_kind = x_kind;
+    a.ldx = ldx;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.epi = *epi;
+    a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
+    return launch_w16(a, p, (hipStream_t)stream);
+  }
   const bool packed_x = x_kind == TI_X_F16_PACKED;
   const bool batched = g32 ? (g32_tile || g32_rowsk) : (packed_x || use_batched(bits, x_kind, M, N, K));
   if (epi->out_packed && (!batched || (epi->kind != TI_EPI_STORE_F16 && epi->kind != TI_EPI_SILU_MUL_F16) ||
@@ -2911,7 +2958,8 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
 extern "C" int ti_epilogue_bytes(void) { return (int)sizeof(ti_epilogue); }
 
 // The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights and for 8 | TI_BITS_G32 (aligned
-// row-major calls): the same predicates as gemm_impl (use_batched, wide_tile, tile_rows, rows_on, w8_route).
+// row-major calls): the same predicates as gemm_impl (use_batched, wide_tile, tile_rows, rows_on, w8_route,
+// w16_route).
 // For bench / profile labels.
 extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len) {
   using namespace ti;
@@ -2921,6 +2969,10 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
     return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: bits %d M %d N %d K %d", bits, M, N, K);
   if (w8_route(bits, x_kind, M)) {
     snprintf(buf, (size_t)len, "gemm_w8_kernel");
+    return TI_OK;
+  }
+  if (w16_route(bits, x_kind, M)) {
+    snprintf(buf, (size_t)len, "gemm_w16_kernel");
     return TI_OK;
   }
   if (q8_0) {   // the fused kernel, more than 16 rows in pieces
