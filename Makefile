@@ -46,6 +46,11 @@ $(BUILD)/k_gemm_w16.o: turboinfer_amd/csrc/kernels/gemm_w16.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
+# gemm_w4a: the flags of gemm_w8 (the fused affine kernel's rounding sequence; k-wave sums and epilogues shared)
+$(BUILD)/k_gemm_w4a.o: turboinfer_amd/csrc/kernels/gemm_w4a.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
 $(BUILD)/k_attention.o: turboinfer_amd/csrc/kernels/attention.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -c $< -o $@

@@ -343,6 +343,20 @@ int ti_gemm_w8_plan_for(int bits, int M, int N, int K, int* rb, int* tpw, int* k
  * TI_ERR_UNSUPPORTED when ti_gemm_w16_rows is 0. */
 int ti_gemm_w16_rows(int M, int N, int K);
 int ti_gemm_w16_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
+/* GGUF Q4_1 weights (4 | TI_BITS_G32 | TI_BITS_AFF) above 16 rows.  ti_gemm_wq_a16 with TI_X_F16 rows and
+ * 17 <= M <= TI_GEMM_MAX_ROWS runs gemm_w4a_kernel: one launch on the tiles, scales and minimums of
+ * ti_wpack_q1_host as they are, the fused kernel's arithmetic (per 32-block one MFMA sum of x (q - 8) from zero,
+ * acc = fmaf(d, sum, acc), acc = fmaf(8 d + m, sum of x, acc), in k order; the k-waves summed in fixed order, so a
+ * second launch gives the same bits), every epilogue kind, any M in the range, under gemm_w8_kernel's conditions
+ * (K % 128 == 0, K <= 65535, N % 16 == 0; tiles, x and out 16-byte aligned, ldx % 8 == 0, ldo % 4 == 0) with scales
+ * 4-byte aligned.  As for Q8_0 nothing is refused because of this route: a call it cannot serve (unaligned operands,
+ * TI_X_F32 / TI_X_F32_RMSNORM rows) runs 16-row pieces of the fused kernel as before.
+ * ti_gemm_w4a_rows: 1 when an M x N x K Q4_1 call with aligned TI_X_F16 rows takes gemm_w4a_kernel, 0 otherwise --
+ * also for every M once the process runs with TI_GEMM_W4A_ROWS=0 (read once), which restores the pieces.
+ * ti_gemm_w4a_plan: the instance such a call launches, in ti_gemm_w8_plan's terms (*rb 2 or 4).
+ * TI_ERR_UNSUPPORTED when ti_gemm_w4a_rows is 0.  ti_gemm_max_rows keeps its values. */
+int ti_gemm_w4a_rows(int M, int N, int K);
+int ti_gemm_w4a_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

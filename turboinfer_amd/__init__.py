@@ -172,7 +172,7 @@ EXPORTED = [
     "ti_guide_step_rows", "ti_engine_add_guide", "ti_engine_remove_guide", "ti_engine_guide_count",
     "ti_engine_serve_requests_guided", "ti_engine_graph_counters",
     "ti_gemm_w8_rows", "ti_gemm_w8_plan", "ti_gemm_w8_rows_for", "ti_gemm_w8_plan_for",
-    "ti_gemm_w16_rows", "ti_gemm_w16_plan",
+    "ti_gemm_w16_rows", "ti_gemm_w16_plan", "ti_gemm_w4a_rows", "ti_gemm_w4a_plan",
 ]
 
 _lib = None
@@ -227,6 +227,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_gemm_w16_rows"):   # (older TI_LIB builds in A/B runs lack the fp16-weight rows kernel)
             L.ti_gemm_w16_rows.argtypes = [i32, i32, i32]
             L.ti_gemm_w16_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
+        if hasattr(L, "ti_gemm_w4a_rows"):   # (older TI_LIB builds in A/B runs lack the Q4_1 rows kernel)
+            L.ti_gemm_w4a_rows.argtypes = [i32, i32, i32]
+            L.ti_gemm_w4a_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
         L.ti_rmsnorm_f16.argtypes = [vp, i32, vp, f32, vp, i32, i32, i32, vp]
         L.ti_rmsnorm_f16_packed.argtypes = [vp, i32, vp, f32, vp, i32, i32, vp]
         L.ti_attn_workspace_bytes.argtypes = [i32, i32, i32, i32]
@@ -467,6 +470,19 @@ def gemm_w16_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
     """(rb, tpw, kwaves, grid) of the gemm_w16_kernel instance an fp16-weight M x N x K call launches."""
     v = [C.c_int() for _ in range(4)]
     check(lib().ti_gemm_w16_plan(M, N, K, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def gemm_w4a_rows(M: int, N: int, K: int) -> bool:
+    """Whether a Q4_1 (4 | BITS_G32 | BITS_AFF) M x N x K call with aligned fp16 rows takes gemm_w4a_kernel (17 ..
+    GEMM_MAX_ROWS rows; never with TI_GEMM_W4A_ROWS=0)."""
+    return bool(lib().ti_gemm_w4a_rows(M, N, K))
+
+
+def gemm_w4a_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
+    """(rb, tpw, kwaves, grid) of the gemm_w4a_kernel instance a Q4_1 M x N x K call launches."""
+    v = [C.c_int() for _ in range(4)]
+    check(lib().ti_gemm_w4a_plan(M, N, K, *[C.byref(x) for x in v]))
     return tuple(x.value for x in v)
 
 

@@ -191,9 +191,9 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
     if ((rc = ti_memcpy_h2d(e->rope_cs, cs.data(), cs.size() * 4, e->s))) return fail(rc);
     if (const char* env = getenv("TI_ATTN_PART")) e->part_on = atoi(env) != 0;
     e->splits_max = e->splits_for(1);
-    // int4 (also group-32): the tile GEMM; INT8 (also group-32): gemm_w8_kernel; fp16 weights: gemm_w16_kernel
+    // int4 (also group-32): the tile GEMM; INT8 (also group-32): gemm_w8_kernel; fp16 weights: gemm_w16_kernel;
+    // Q4_1 (affine group-32): gemm_w4a_kernel
     e->pf_rows = chunk_rows_max(c);
-    // (affine group-32 runs the fused kernel only: prompt chunks of its 16 rows)
     e->rows_cap = std::max(B, e->pf_rows);
     const int R = e->rows_cap;
     const int Rp = (R + 15) / 16 * 16;   // packed operands hold whole 16-row blocks

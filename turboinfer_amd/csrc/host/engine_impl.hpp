@@ -343,13 +343,17 @@ bool packed_rows(const ti_engine* e, int M);
 // Rows one GEMM launch takes on this engine's weights beyond the fused kernel's 16: int4 (also group-32) the
 // rows / tile kernels, INT8 group-128 and group-32 (Q8_0 blocks) gemm_w8_kernel (ti_gemm_w8_rows_for: off
 // with TI_GEMM_W8_ROWS=0), fp16 weights gemm_w16_kernel (ti_gemm_w16_rows: off with TI_GEMM_W16_ROWS=0); the
-// largest prompt chunk.  Everything else (affine group-32, compat engines) runs 16-row fused pieces.
+// Q4_1 (affine group-32) gemm_w4a_kernel (ti_gemm_w4a_rows: off with TI_GEMM_W4A_ROWS=0); the largest prompt
+// chunk.  Everything else (compat engines) runs 16-row fused pieces.
 inline bool w8_rows(const ti_engine_config& c) {
   return (c.bits & ~TI_BITS_G32) == 8 && ti_gemm_w8_rows_for(c.bits, 17, 16, 128) != 0;
 }
 inline bool w16_rows(const ti_engine_config& c) { return c.bits == 16 && ti_gemm_w16_rows(17, 16, 128) != 0; }
+inline bool w4a_rows(const ti_engine_config& c) {
+  return c.bits == (4 | TI_BITS_G32 | TI_BITS_AFF) && ti_gemm_w4a_rows(17, 16, 128) != 0;
+}
 inline int chunk_rows_max(const ti_engine_config& c) {
-  return (c.bits & ~TI_BITS_G32) == 4 || w8_rows(c) || w16_rows(c) ? TI_GEMM_MAX_ROWS : 16;
+  return (c.bits & ~TI_BITS_G32) == 4 || w8_rows(c) || w16_rows(c) || w4a_rows(c) ? TI_GEMM_MAX_ROWS : 16;
 }
 int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind, int ldx, const float* nw,
               const ti_epilogue& epi, size_t out_elem, bool last_gets_ctr);

@@ -1,5 +1,6 @@
 // gemm_shared.hpp -- what the GEMM kernels of gemv.hip (int4 tile kernel), gemm_w8.hip (INT8 rows
-// kernel) and gemm_w16.hip (fp16-weight rows kernel) have in common and is independent of the weight format: the launch arguments, the swizzled
+// kernel), gemm_w16.hip (fp16-weight rows kernel) and gemm_w4a.hip (Q4_1 rows kernel) have in common and is
+// independent of the weight format: the launch arguments, the swizzled
 // activation image in LDS, the staged epilogue of a 64 x 16 output block.
 #pragma once
 #include "common.hpp"
@@ -170,5 +171,15 @@ bool w16_rows_on();   // TI_GEMM_W16_ROWS (0: the route is off)
 W16Plan w16_plan(int M, int N, int K, int cus);
 int w16_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
 int launch_w16(const GemvArgs& a, const W16Plan& p, hipStream_t s);
+
+// ------------------------------------------------------------ gemm_w4a.hip (Q4_1 rows kernel), host side
+// The instance of gemm_w4a_kernel a call takes, in W8Plan's terms.
+struct W4aPlan {
+  int rb, tpw, kw, n_cb, n_rb, grid, lds;
+};
+bool w4a_rows_on();   // TI_GEMM_W4A_ROWS (0: the route is off)
+W4aPlan w4a_plan(int M, int N, int K, int cus);
+int w4a_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
+int launch_w4a(const GemvArgs& a, const W4aPlan& p, hipStream_t s);
 
 }  // namespace ti

@@ -2569,6 +2569,7 @@ extern "C" int ti_gemm_prepare(void) {
                  "hipFuncSetAttribute(gemv_wq_kernel)");
   if (const int rc = w8_prepare()) return rc;
   if (const int rc = w16_prepare()) return rc;
+  if (const int rc = w4a_prepare()) return rc;
   g_prepared.fetch_or(bit, std::memory_order_acq_rel);
   return TI_OK;
 }
@@ -2645,6 +2646,27 @@ extern "C" int ti_gemm_w16_plan(int M, int N, int K, int* rb, int* tpw, int* kwa
   if (!ti_gemm_w16_rows(M, N, K))
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_w16_plan: M=%d N=%d K=%d is not a gemm_w16_kernel call", M, N, K);
   const ti::W16Plan p = ti::w16_plan(M, N, K, query_cus());
+  *rb = p.rb;
+  *tpw = p.tpw;
+  *kwaves = p.kw;
+  *grid = p.grid;
+  return TI_OK;
+}
+// Q4_1 (affine group-32 int4) fp16 rows above 16: gemm_w4a_kernel (gemm_w4a.hip); TI_GEMM_W4A_ROWS=0 turns the
+// route off (16-row fused pieces).
+static bool w4a_route(int bits, int x_kind, int M) {
+  return bits == (4 | TI_BITS_G32 | TI_BITS_AFF) && x_kind == TI_X_F16 && M > 16 && M <= TI_GEMM_MAX_ROWS &&
+         ti::w4a_rows_on();
+}
+extern "C" int ti_gemm_w4a_rows(int M, int N, int K) {
+  return w4a_route(4 | TI_BITS_G32 | TI_BITS_AFF, TI_X_F16, M) && N >= 16 && !(N & 15) && K >= 128 && !(K & 127) &&
+                 K <= 0xffff ? 1 : 0;
+}
+extern "C" int ti_gemm_w4a_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
+  if (!rb || !tpw || !kwaves || !grid) return ti_set_error(TI_ERR_ARG, "ti_gemm_w4a_plan: null pointer");
+  if (!ti_gemm_w4a_rows(M, N, K))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_w4a_plan: M=%d N=%d K=%d is not a gemm_w4a_kernel call", M, N, K);
+  const ti::W4aPlan p = ti::w4a_plan(M, N, K, query_cus());
   *rb = p.rb;
   *tpw = p.tpw;
   *kwaves = p.kw;
@@ -2729,7 +2751,8 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: bits must be 4, 8 or 16 (+ TI_BITS_G32 for 4 / 8, + TI_BITS_AFF "
                         "for 4 | G32; got %d)", bits);
   // group-32: int4 fp16 rows from tile_rows() on run on the tile kernel, everything else on the
-  // fused kernel (more than 16 rows: in 16-row pieces, below); affine blocks on the fused kernel only
+  // fused kernel (more than 16 rows: in 16-row pieces, below); affine blocks on the fused kernel and, fp16 rows
+  // above 16, on gemm_w4a_kernel (g32_w4a below)
   const bool g32_tile = g32 && !aff && bits == 4 && x_kind == TI_X_F16 && M >= tile_rows() && !epi->out_packed;
   // group-32 int4 fp16 rows 17..64: the batched-rows kernel (TI_GEMM_G32_ROWS=0: fused pieces, A/B knob)
   const bool g32_rowsk = g32 && !aff && bits == 4 && x_kind == TI_X_F16 && M > 16 && M < tile_rows() &&
@@ -2798,7 +2821,11 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
   // group-32 INT8 (Q8_0) fp16 rows above 16: the kernel's group-32 instance where it can serve the call,
   // else (unlike group-128 INT8, which has nothing else there) the fused pieces below
   const bool g32_w8 = g32 && w8_route(bits, x_kind, M) && w8_vec && !epi->out_packed && !fold_out && !fold_in;
-  if (g32 && !g32_tile && !g32_rowsk && !g32_w8 && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
+  // affine group-32 int4 (Q4_1) fp16 rows above 16: gemm_w4a_kernel where it can serve the call (vector accesses
+  // as above, the scale / minimum pairs as dwords), else the fused pieces below
+  const bool g32_w4a = aff && w4a_route(bits | TI_BITS_G32 | TI_BITS_AFF, x_kind, M) && w8_vec && !((uintptr_t)scales & 3) &&
+                       !epi->out_packed && !fold_out && !fold_in;
+  if (g32 && !g32_tile && !g32_rowsk && !g32_w8 && !g32_w4a && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
     if (x_kind == TI_X_ATTN_SPLITS || x_kind == TI_X_F16_FOLDED || epi->out_packed)
       return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: group-32 rows > 16 need plain x rows");
     const size_t x_elem = x_kind == TI_X_F16 ? 2 : 4;
@@ -2846,6 +2873,27 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     a.epi = *epi;
     a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
     return launch_w8(a, p, (hipStream_t)stream);
+  }
+  if (g32_w4a) {   // Q4_1 rows above 16: gemm_w4a_kernel
+    const W4aPlan p = w4a_plan(M, N, K, query_cus());
+    if (p.lds > 64 * 1024) {   // no-op once this device is prepared
+      const int rc = ti_gemm_prepare();
+      if (rc != TI_OK) return rc;
+    }
+    GemvArgs a;
+    a.tiles = (const u32x4*)tiles;
+    a.scales = scales;
+    a.x = x;
+    a.norm_w = norm_w;
+    a.eps = eps;
+    a.x_kind = x_kind;
+    a.ldx = ldx;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.epi = *epi;
+    a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
+    return launch_w4a(a, p, (hipStream_t)stream);
   }
   if (!g32 && w16_route(bits, x_kind, M)) {   // fp16-weight rows above 16: gemm_w16_kernel (nothing else serves them)
     if (epi->out_packed || fold_out || fold_in)
@@ -2957,15 +3005,15 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
 
 extern "C" int ti_epilogue_bytes(void) { return (int)sizeof(ti_epilogue); }
 
-// The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights and for 8 | TI_BITS_G32 (aligned
-// row-major calls): the same predicates as gemm_impl (use_batched, wide_tile, tile_rows, rows_on, w8_route,
-// w16_route).
+// The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights, for 8 | TI_BITS_G32 and for
+// 4 | TI_BITS_G32 | TI_BITS_AFF (aligned row-major calls): the same predicates as gemm_impl (use_batched, wide_tile,
+// tile_rows, rows_on, w8_route, w16_route, w4a_route).
 // For bench / profile labels.
 extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len) {
   using namespace ti;
-  const bool q8_0 = bits == (8 | TI_BITS_G32);
+  const bool q8_0 = bits == (8 | TI_BITS_G32), q4_1 = bits == (4 | TI_BITS_G32 | TI_BITS_AFF);
   if (!buf || len < 1) return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: null buffer");
-  if ((bits != 4 && bits != 8 && bits != 16 && !q8_0) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
+  if ((bits != 4 && bits != 8 && bits != 16 && !q8_0 && !q4_1) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
     return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: bits %d M %d N %d K %d", bits, M, N, K);
   if (w8_route(bits, x_kind, M)) {
     snprintf(buf, (size_t)len, "gemm_w8_kernel");
@@ -2973,6 +3021,11 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
   }
   if (w16_route(bits, x_kind, M)) {
     snprintf(buf, (size_t)len, "gemm_w16_kernel");
+    return TI_OK;
+  }
+  if (q4_1) {   // gemm_w4a_kernel, else the fused kernel (more than 16 rows in pieces)
+    if (w4a_route(bits, x_kind, M)) snprintf(buf, (size_t)len, "gemm_w4a_kernel");
+    else snprintf(buf, (size_t)len, "gemv_wq_kernel<4,%d>", gemv_xmode(x_kind, M, K));
     return TI_OK;
   }
   if (q8_0) {   // the fused kernel, more than 16 rows in pieces
