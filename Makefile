@@ -32,7 +32,7 @@ $(BUILD)/k_ops_exact.o: turboinfer_amd/csrc/kernels/ops_exact.hip $(HDRS)
 
 # gemv: preload its leading kernel arguments into SGPRs (gfx950 kernarg preload).
 # gemv, attention and qkv_attn compile without fp contraction (the rounding sequence the parity tests pin).
-$(BUILD)/k_gemv.o: turboinfer_amd/csrc/kernels/gemv.hip $(HDRS)
+$(BUILD)/k_gemv.o: turboinfer_amd/csrc/kernels/gemv.hip turboinfer_amd/csrc/kernels/gemv_wq_body.inc $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -mllvm -amdgpu-kernarg-preload-count=16 -c $< -o $@
 
@@ -48,6 +48,11 @@ $(BUILD)/k_gemm_w16.o: turboinfer_amd/csrc/kernels/gemm_w16.hip $(HDRS)
 
 # gemm_w4a: the flags of gemm_w8 (the fused affine kernel's rounding sequence; k-wave sums and epilogues shared)
 $(BUILD)/k_gemm_w4a.o: turboinfer_amd/csrc/kernels/gemm_w4a.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# wsynth_mx: scalar fp32 arithmetic that must match the host packer bit for bit (no contraction, no packed fp32)
+$(BUILD)/k_wsynth_mx.o: turboinfer_amd/csrc/kernels/wsynth_mx.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 

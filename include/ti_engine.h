@@ -67,6 +67,13 @@ int ti_engine_set_tensor_q(ti_engine* e, int slot, int layer, const int8_t* q, c
  * 4 | TI_BITS_G32 | TI_BITS_AFF: q uint8 [K][N_src] (0..15), d and m fp16 [K/32][N_src],
  * weight = d * q + m (ti_wpack_q1_host). */
 int ti_engine_set_tensor_q1(ti_engine* e, int slot, int layer, const uint8_t* q, const uint16_t* d, const uint16_t* m);
+/* MXFP4 blocks (ggml's GGML_TYPE_MXFP4 / OCP microscaling FP4) kept exact on an engine with bits
+ * 4 | TI_BITS_G32 | TI_BITS_MX: codes uint8 [K][N_src] (e2m1, 0..15), scales uint8 [K/32][N_src] (e8m0),
+ * weight = 2^(scale - 127) * e2m1(code) (ti_wpack_mx_host; its argument errors).  Such an engine runs every
+ * projection on the fused kernel's MX instance: 16-row chunks for prompts and batched steps, no folded
+ * rms_norm hand-off and no fused QKV + attention launch (ti_engine_set_qkv_attn reports 0).  ti_engine_synth
+ * and ti_engine_set_tensor quantize fp32 values per block by ti_wpack_host's rule. */
+int ti_engine_set_tensor_mx(ti_engine* e, int slot, int layer, const uint8_t* codes, const uint8_t* scales);
 /* Synthetic model of SURVEY 8(d) generated on the device (bit-identical to the oracle's
  * or_model_synth for the same seed / jitter). */
 int ti_engine_synth(ti_engine* e, uint64_t seed, float norm_jitter);

@@ -127,6 +127,24 @@ int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_src, int N_
 /* q uint8 [K][N_src] (0..15), d and m fp16 [K/32][N_src]: weight(k, c) = d * q + m. */
 int ti_wpack_q1_host(const uint8_t* q, const uint16_t* d, const uint16_t* m, int K, int N_src, int N_total, int row_map,
                      int row_offset, void* tiles, uint16_t* scales);
+/* OCP microscaling FP4 (MXFP4; ggml's GGML_TYPE_MXFP4 blocks): bits = 4 | TI_BITS_G32 | TI_BITS_MX.  A block is
+ * 32 weights of one output row, each an e2m1 nibble (bit 3 sign, bits 0-2 the magnitude code of
+ * {0, .5, 1, 1.5, 2, 3, 4, 6}), and one e8m0 byte e: weight = 2^(e - 127) * e2m1(nibble), 1 <= e <= 254.
+ * Tiles: the group-32 int4 layout and k order above with the raw e2m1 code where Q4_0 keeps q + 8.  Scales: the
+ * e bytes, [N/16][K/128][4][16] uint8 (ti_wpack_scale_bytes; half of Q4_0's) behind the uint16_t* of the shared
+ * signatures.  Dequantization to fp16 is exact (v_cvt_scalef32_pk_f16_fp4 at scale 1), the block scale
+ * bit_cast<float>(e << 23) is applied in fp32 and there is no offset term.  Fused kernel only (1..16 rows; more
+ * rows run in 16-row pieces); no tile GEMM, no packed rows, no fused QKV + attention launch.
+ * ti_wpack_host with these bits quantizes fp32 weights per 32-block (scale_mode ignored): e = floor(log2(absmax))
+ * - 2 + 127 clamped to [1, 254] (the OCP rule: e2m1's largest exponent is 2; an all-zero block stores 127), code =
+ * sign | round-to-nearest-even of |w| / 2^(e - 127) onto the e2m1 grid (ties to the even code), saturating at 6;
+ * the sign bit is set for w < 0. */
+#define TI_BITS_MX 256
+/* Exact MXFP4 blocks: codes uint8 [K][N_src] (0..15), e uint8 [K/32][N_src].  A block whose 32 codes are all +-0
+ * may carry any e (127 is stored); any other block with e outside [1, 254] is TI_ERR_ARG (255 is the format's
+ * NaN, 0 is below what e << 23 expresses as a normal fp32). */
+int ti_wpack_mx_host(const uint8_t* codes, const uint8_t* e, int K, int N_src, int N_total, int row_map,
+                     int row_offset, void* tiles, uint8_t* scales);
 
 /* The synthetic model of SURVEY 8(d) generated straight into device tiles:
  * element (k, c) of tensor `tensor_id` = u(seed, tensor_id, k*N_src + c) * amp,

@@ -13,7 +13,7 @@
 //   * tensor data starts at the first general.alignment (default 32) boundary after the
 //     tensor infos and tensor i sits at data_start + offset_i (the reference seeks each offset
 //     relative to where the previous read ended, :842, correct for the first tensor only);
-//   * Q4_0, Q4_1 and Q8_0 blocks are dequantized to fp32 (ggml's block formats: 32 weights per
+//   * Q4_0, Q4_1, Q8_0 and MXFP4 (type 39) blocks are dequantized to fp32 (ggml's block formats: 32 weights per
 //     block, an fp16 scale d (and min m), y = (q - 8) d, q d + m, q d); the reference declares
 //     these types fp32 and reads the packed bytes as floats (:165-182, 817-829).  BF16 is
 //     widened to fp32.  Other types raise.
@@ -39,7 +39,7 @@ enum GgufValue : uint32_t {
   kU8 = 0, kI8 = 1, kU16 = 2, kI16 = 3, kU32 = 4, kI32 = 5, kF32 = 6, kBool = 7, kStr = 8, kArr = 9,
   kU64 = 10, kI64 = 11, kF64 = 12
 };
-enum GgmlType : uint32_t { kTF32 = 0, kTF16 = 1, kTQ4_0 = 2, kTQ4_1 = 3, kTQ8_0 = 8, kTBF16 = 30 };
+enum GgmlType : uint32_t { kTF32 = 0, kTF16 = 1, kTQ4_0 = 2, kTQ4_1 = 3, kTQ8_0 = 8, kTBF16 = 30, kTMXFP4 = 39 };
 
 struct Reader {
   std::ifstream f;
@@ -156,6 +156,20 @@ void dequant_q8_0(const uint8_t* b, size_t nblk, float* y) {
   }
 }
 
+// MXFP4 (GGML_TYPE_MXFP4, block_mxfp4 { uint8_t e; uint8_t qs[16]; }): 2^(e - 127) * e2m1(nibble), element j in the
+// low nibble of qs[j], element j + 16 in the high one.  Exact in fp32 for 1 <= e <= 254.
+void dequant_mxfp4(const uint8_t* b, size_t nblk, float* y) {
+  static const float kE2M1[16] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f,
+                                  -0.0f, -0.5f, -1.0f, -1.5f, -2.0f, -3.0f, -4.0f, -6.0f};
+  for (size_t i = 0; i < nblk; ++i, b += 17, y += 32) {
+    const float d = std::ldexp(1.0f, (int)b[0] - 127);
+    for (int j = 0; j < 16; ++j) {
+      y[j] = kE2M1[b[1 + j] & 0x0f] * d;
+      y[j + 16] = kE2M1[b[1 + j] >> 4] * d;
+    }
+  }
+}
+
 struct Info {
   std::string name;
   std::vector<size_t> dims;   // reversed: row-major
@@ -167,12 +181,12 @@ size_t stored_bytes(uint32_t type, size_t n, const std::string& name) {
   switch (type) {
     case kTF32: return n * 4;
     case kTF16: case kTBF16: return n * 2;
-    case kTQ4_0: case kTQ4_1: case kTQ8_0:
+    case kTQ4_0: case kTQ4_1: case kTQ8_0: case kTMXFP4:
       if (n % 32) throw std::runtime_error("GGUF: tensor " + name + " is not a whole number of 32-weight blocks");
-      return n / 32 * (type == kTQ4_0 ? 18 : type == kTQ4_1 ? 20 : 34);
+      return n / 32 * (type == kTQ4_0 ? 18 : type == kTQ4_1 ? 20 : type == kTMXFP4 ? 17 : 34);
     default:
       throw std::runtime_error("GGUF: tensor " + name + " has unsupported ggml type " + std::to_string(type) +
-                               " (supported: F32, F16, BF16, Q4_0, Q4_1, Q8_0)");
+                               " (supported: F32, F16, BF16, Q4_0, Q4_1, Q8_0, MXFP4)");
   }
 }
 
@@ -253,6 +267,7 @@ ModelData ModelLoader::load_gguf(const std::string& file_path) {
     if (t.type == kTQ4_0) dequant_q4_0(raw.data(), n / 32, y);
     else if (t.type == kTQ4_1) dequant_q4_1(raw.data(), n / 32, y);
     else if (t.type == kTQ8_0) dequant_q8_0(raw.data(), n / 32, y);
+    else if (t.type == kTMXFP4) dequant_mxfp4(raw.data(), n / 32, y);
     else if (t.type == kTBF16)
       for (size_t i = 0; i < n; ++i) {
         const uint32_t bits = (uint32_t)(raw[2 * i] | (raw[2 * i + 1] << 8)) << 16;

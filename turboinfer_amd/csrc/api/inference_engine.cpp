@@ -349,6 +349,35 @@ bool recover_q41(const std::vector<float>& w, size_t K, size_t N, std::vector<in
   return true;
 }
 
+// GGUF MXFP4 checkpoints (gguf.cpp dequant_mxfp4): every block is 2^(e - 127) * e2m1(code).  A linear weight is MX
+// when every 32-block has such an e with all 32 values on the e2m1 grid.  The smallest valid e is taken:
+// e0 = floor(log2 absmax) - 2 + 127, the one that puts absmax at 4 or 6 -- a smaller e puts absmax past 6, and the
+// grid of any larger e, cut at absmax, is a subset of e0's, so e0 fits whenever any e does.  Every weight is verified
+// exactly; any valid e reproduces the same weights.  An all-zero block keeps e = 127.
+bool recover_mx(const std::vector<float>& w, size_t K, size_t N, std::vector<int8_t>& q, std::vector<uint8_t>& e) {
+  if (K % 32 || w.size() != K * N) return false;
+  static const float kGrid[8] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f};
+  q.assign(K * N, 0);
+  e.assign(K / 32 * N, 127);
+  for (size_t n = 0; n < N; ++n)
+    for (size_t b = 0; b < K / 32; ++b) {
+      float amax = 0.0f;
+      for (size_t k = 32 * b; k < 32 * b + 32; ++k) amax = std::max(amax, std::fabs(w[k * N + n]));
+      if (!std::isfinite(amax)) return false;
+      const int eb = amax > 0.0f ? std::ilogb(amax) - 2 + 127 : 127;
+      if (eb < 1 || eb > 254) return false;
+      e[b * N + n] = (uint8_t)eb;
+      for (size_t k = 32 * b; k < 32 * b + 32; ++k) {
+        const float x = w[k * N + n], v = std::ldexp(std::fabs(x), 127 - eb);
+        int c = 0;
+        while (c < 8 && kGrid[c] != v) ++c;
+        if (c == 8) return false;
+        q[k * N + n] = (int8_t)(c | (std::signbit(x) ? 8 : 0));
+      }
+    }
+  return true;
+}
+
 bool is_int(const core::Tensor& t) {
   return t.dtype() == core::DataType::kInt8 || t.dtype() == core::DataType::kInt32 ||
          t.dtype() == core::DataType::kInt16 || t.dtype() == core::DataType::kUInt8;
@@ -376,10 +405,12 @@ class InferenceEngineImpl {
   struct Blocks {
     std::vector<int8_t> q;
     std::vector<uint16_t> d, m;   // m: Q4_1 block minimums
+    std::vector<uint8_t> e;       // MXFP4 block scales (q then holds the e2m1 codes)
   };
   std::map<const core::Tensor*, Blocks> g32;
 
   static bool recover(const std::vector<float>& w, size_t K, size_t N, int bits, Blocks& b) {
+    if (bits & TI_BITS_MX) return recover_mx(w, K, N, b.q, b.e);
     return (bits & TI_BITS_AFF) ? recover_q41(w, K, N, b.q, b.d, b.m)
                                 : recover_g32(w, K, N, bits & ~TI_BITS_G32, b.q, b.d);
   }
@@ -419,7 +450,10 @@ class InferenceEngineImpl {
         g32.erase(it);
       }
       if (!b.q.empty() || recover(api::to_f32(t), K, N, bits, b)) {
-        if (bits & TI_BITS_AFF)
+        if (bits & TI_BITS_MX)
+          check(ti_engine_set_tensor_mx(eng, slot, layer, reinterpret_cast<const uint8_t*>(b.q.data()), b.e.data()),
+                "ti_engine_set_tensor_mx");
+        else if (bits & TI_BITS_AFF)
           check(ti_engine_set_tensor_q1(eng, slot, layer, reinterpret_cast<const uint8_t*>(b.q.data()), b.d.data(),
                                         b.m.data()),
                 "ti_engine_set_tensor_q1");
@@ -492,7 +526,7 @@ class InferenceEngineImpl {
     cfg.rope_theta = md.rope_theta > 0.0f ? md.rope_theta : 10000.0f;
     cfg.eps = 1e-5f;
     const int bits = engine_option(md, "turboinfer.weight_bits", "TI_WEIGHT_BITS", 0);
-    cfg.bits = bits == 8 || bits == 16 ? bits : 4;
+    cfg.bits = bits == 8 || bits == 16 || bits == (4 | TI_BITS_G32 | TI_BITS_MX) ? bits : 4;
     kv_bits = kv_bits_option(md);
     lookahead = lookahead_option(md, kv_bits);
     share_prefix = share_prefix_option(md, kv_bits);
@@ -546,15 +580,20 @@ class InferenceEngineImpl {
           if (x < -8.0f || x > 7.0f) bits = 8;
       } else if (gguf_src && q0) {   // Q4_0 / Q4_1 / Q8_0 checkpoint: keep its blocks
         const size_t kvd = k0 ? k0->shape().total_size() / H : H;
+        // Order: Q4_0, Q4_1, MXFP4, Q8_0.  Q4_0 first, so a Q4_0 file stays Q4_0 (its blocks hold q = 5 or 7 times d,
+        // which no e2m1 grid holds beside 8 d, so they would not pass as MX anyway); MXFP4 before Q8_0, because every MX
+        // block is also integers of [-12, 12] times a power of two, i.e. a valid Q8_0 block.
         if (all_g32(m, L, H, H, kvd, I, V, 4 | TI_BITS_G32)) bits = 4 | TI_BITS_G32;
         else if (all_g32(m, L, H, H, kvd, I, V, 4 | TI_BITS_G32 | TI_BITS_AFF)) bits = 4 | TI_BITS_G32 | TI_BITS_AFF;
+        else if (all_g32(m, L, H, H, kvd, I, V, 4 | TI_BITS_G32 | TI_BITS_MX)) bits = 4 | TI_BITS_G32 | TI_BITS_MX;
         else if (all_g32(m, L, H, H, kvd, I, V, 8 | TI_BITS_G32)) bits = 8 | TI_BITS_G32;
       }
     }
     if (bits != 4 && bits != 8 && bits != 16 && bits != (4 | TI_BITS_G32) && bits != (8 | TI_BITS_G32) &&
-        bits != (4 | TI_BITS_G32 | TI_BITS_AFF))
+        bits != (4 | TI_BITS_G32 | TI_BITS_AFF) && bits != (4 | TI_BITS_G32 | TI_BITS_MX))
       throw std::runtime_error(
-          "InferenceEngine: weight_bits must be 4, 8, 16, 4 / 8 | 32 (group-32 blocks) or 4 | 32 | 64 (Q4_1 blocks)");
+          "InferenceEngine: weight_bits must be 4, 8, 16, 4 / 8 | 32 (group-32 blocks), 4 | 32 | 64 (Q4_1 blocks) or "
+          "4 | 32 | 256 (MXFP4 blocks)");
     cfg.vocab = (int)V;
     cfg.hidden = (int)H;
     cfg.layers = (int)L;
@@ -1046,8 +1085,8 @@ std::string InferenceEngine::performance_stats() const {
   if (im.total_time_ms > 0.0f)
     os << "  Average Tokens/Second: " << (im.total_tokens / (im.total_time_ms / 1000.0f)) << "\n";
   os << "  Peak Tokens/Second: " << im.peak_tps << "\n";
-  os << "  Device Memory: " << (memory_usage() / (1024.0 * 1024.0)) << " MB (weights " << (im.cfg.bits & ~(TI_BITS_G32 | TI_BITS_AFF))
-     << "-bit" << ((im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << (im.kv_bits == 8 ? ", fp8 KV, " : ", fp16 KV, ") << im.capacity
+  os << "  Device Memory: " << (memory_usage() / (1024.0 * 1024.0)) << " MB (weights " << (im.cfg.bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX))
+     << "-bit" << ((im.cfg.bits & TI_BITS_MX) ? " MXFP4 blocks" : (im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << (im.kv_bits == 8 ? ", fp8 KV, " : ", fp16 KV, ") << im.capacity
      << " stream(s) x " << im.cfg.max_seq << " slots)\n";
   os << "  Mode: " << (im.compat ? "reference_compat (plumbing model)" : "llama decode") << "\n";
   return os.str();

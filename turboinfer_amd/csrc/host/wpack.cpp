@@ -6,6 +6,7 @@
 // formula -- scale = absmax / 7 (int4) or / 127 (int8), q = clamp(round(x / scale)) with
 // std::round (half away from zero) -- is applied per group of 128 k of one output column,
 // and the result is packed two nibbles per byte with an fp16 scale per group.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -39,11 +40,12 @@ inline uint16_t to_half(float f) {
 
 extern "C" size_t ti_wpack_tile_bytes(int bits, int K, int N) {
   if (K <= 0 || N <= 0) return 0;
-  return (size_t)(N / 16) * (size_t)(K / 128) * 256u * (size_t)(bits & ~(TI_BITS_G32 | TI_BITS_AFF));
+  return (size_t)(N / 16) * (size_t)(K / 128) * 256u * (size_t)(bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX));
 }
 
 extern "C" size_t ti_wpack_scale_bytes(int bits, int K, int N) {
   if (bits == 16 || K <= 0 || N <= 0) return 0;
+  if (bits & TI_BITS_MX) return (size_t)(N / 16) * (size_t)(K / 128) * 64u;   // MXFP4: one e8m0 byte per block
   return (size_t)(N / 16) * (size_t)(K / 128) * 16u * sizeof(uint16_t) * ((bits & TI_BITS_G32) ? 4u : 1u) *
          ((bits & TI_BITS_AFF) ? 2u : 1u);   // affine group-32: the block minimums follow the scales
 }
@@ -80,6 +82,53 @@ void pack_row(uint8_t* tile, int bits, bool g32, int r, const int8_t* q) {
 }
 
 }  // namespace
+
+// MXFP4 (ti_hip.h): the e2m1 code of v, round-to-nearest-even onto {0, .5, 1, 1.5, 2, 3, 4, 6} (a tie goes to the
+// even code), saturating at 6; bit 3 is the sign of v < 0.
+static uint8_t mx_code(float v) {
+  static const float grid[8] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f};
+  const float a = std::fabs(v);
+  int c = 0;
+  while (c < 7) {
+    const float mid = 0.5f * (grid[c] + grid[c + 1]);
+    if (a > mid || (a == mid && (c & 1))) ++c;
+    else break;
+  }
+  return (uint8_t)(c | (v < 0.0f ? 8 : 0));
+}
+
+extern "C" int ti_wpack_mx_host(const uint8_t* codes, const uint8_t* e, int K, int N_src, int N_total, int row_map,
+                                int row_offset, void* tiles, uint8_t* scales) {
+  if (!codes || !e || !tiles || !scales) return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: null pointer");
+  if (K <= 0 || (K & 127) || N_total <= 0 || (N_total & 15) || N_src <= 0)
+    return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: K %% 128 / N %% 16 (K=%d N_total=%d)", K, N_total);
+  if (row_map == TI_ROWS_INTERLEAVE8 && (N_src & 7)) return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: interleave needs N %% 8 == 0");
+  if (map_row(N_src - 1, row_map, row_offset) >= N_total || row_offset < 0)
+    return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: rows do not fit N_total");
+  const int KT = K / 128;
+  uint8_t* tb = static_cast<uint8_t*>(tiles);
+  int8_t col[128];
+  for (int c = 0; c < N_src; ++c) {
+    const int n = map_row(c, row_map, row_offset), nt = n >> 4, r = n & 15;
+    for (int g = 0; g < KT; ++g) {
+      for (int s4 = 0; s4 < 4; ++s4) {
+        bool zero = true;
+        for (int i = 32 * s4; i < 32 * s4 + 32; ++i) {
+          const int v = codes[(size_t)(g * 128 + i) * N_src + c];
+          if (v > 15) return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: code %d outside [0, 15]", v);
+          zero = zero && !(v & 7);
+          col[i] = (int8_t)(v - 8);   // (pack_row stores q + 8: the raw code)
+        }
+        const int eb = e[(size_t)(g * 4 + s4) * N_src + c];
+        if (!zero && (eb < 1 || eb > 254))
+          return ti_set_error(TI_ERR_ARG, "ti_wpack_mx_host: block scale e = %d outside [1, 254]", eb);
+        scales[(((size_t)nt * KT + g) * 4 + s4) * 16 + r] = (uint8_t)(zero ? 127 : eb);
+      }
+      pack_row(tb + ((size_t)nt * KT + g) * 1024, 4, true, r, col);
+    }
+  }
+  return TI_OK;
+}
 
 extern "C" int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_src, int N_total, int bits, int row_map,
                                int row_offset, void* tiles, uint16_t* scales) {
@@ -137,6 +186,24 @@ extern "C" int ti_wpack_host(const float* w, int K, int N_src, int N_total, int 
         }
       }
     return ti_wpack_q1_host(q.data(), d.data(), m.data(), K, N_src, N_total, row_map, row_offset, tiles, scales);
+  }
+  if (bits == (4 | TI_BITS_G32 | TI_BITS_MX)) {
+    // fp32 weights onto an MXFP4 engine: the OCP rule per 32-block (ti_hip.h), then packed exactly
+    if (K <= 0 || (K & 127) || N_src <= 0) return ti_set_error(TI_ERR_ARG, "ti_wpack_host: K %% 128 (K=%d)", K);
+    std::vector<uint8_t> q((size_t)K * N_src), e((size_t)(K / 32) * N_src);
+    for (int c = 0; c < N_src; ++c)
+      for (int b = 0; b < K / 32; ++b) {
+        float amax = 0.0f;
+        for (int i = 0; i < 32; ++i) amax = std::max(amax, std::fabs(w[(size_t)(b * 32 + i) * N_src + c]));
+        if (!std::isfinite(amax)) return ti_set_error(TI_ERR_ARG, "ti_wpack_host: non-finite weight in an MXFP4 block");
+        const int eb = amax > 0.0f ? std::min(254, std::max(1, std::ilogb(amax) - 2 + 127)) : 127;
+        e[(size_t)b * N_src + c] = (uint8_t)eb;
+        for (int i = 0; i < 32; ++i) {
+          const size_t at = (size_t)(b * 32 + i) * N_src + c;
+          q[at] = mx_code(std::ldexp(w[at], 127 - eb));
+        }
+      }
+    return ti_wpack_mx_host(q.data(), e.data(), K, N_src, N_total, row_map, row_offset, tiles, (uint8_t*)scales);
   }
   const bool g32 = (bits & TI_BITS_G32) != 0;
   bits &= ~TI_BITS_G32;

@@ -41,6 +41,25 @@ __device__ __forceinline__ f16x8 deq_int4_raw(uint32_t w, uint32_t magic) {
   return __builtin_bit_cast(f16x8, r);
 }
 
+// MXFP4 (TI_BITS_MX): the same word layout with the raw e2m1 code per nibble.  v_cvt_scalef32_pk_f16_fp4 at scale
+// 1 widens the two nibbles of one byte exactly (every e2m1 value is an fp16 value): byte b holds nibbles 2b and
+// 2b + 1, i.e. the element pairs (0, 2), (4, 6), (1, 3), (5, 7) for b = 0..3; four half-word picks
+// put them back in k order (4 conversions + 4 v_perm / v_pack per 8 weights, no offset to remove afterwards).
+__device__ __forceinline__ f16x8 deq_mxfp4(uint32_t w) {
+  const uint32_t c0 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 0));
+  const uint32_t c1 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 1));
+  const uint32_t c2 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 2));
+  const uint32_t c3 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, 3));
+  u32x4 r;   // (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first)
+  r[0] = __builtin_amdgcn_perm(c2, c0, 0x05040100u);   // elements 0, 1
+  r[1] = __builtin_amdgcn_perm(c2, c0, 0x07060302u);   // elements 2, 3
+  r[2] = __builtin_amdgcn_perm(c3, c1, 0x05040100u);   // elements 4, 5
+  r[3] = __builtin_amdgcn_perm(c3, c1, 0x07060302u);   // elements 6, 7
+  return __builtin_bit_cast(f16x8, r);
+}
+// The e8m0 block scale as fp32: 2^(e - 127) for 1 <= e <= 254.
+__device__ __forceinline__ float e8m0_to_f32(uint32_t e) { return __builtin_bit_cast(float, e << 23); }
+
 template <int BITS>
 __device__ __forceinline__ f16x8 dequant_step(const u32x4 (&w)[BITS / 4], int s4, uint32_t magic) {
   if constexpr (BITS == 4) {
