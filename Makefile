@@ -51,6 +51,11 @@ $(BUILD)/k_gemm_w4a.o: turboinfer_amd/csrc/kernels/gemm_w4a.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
+# gemm_mx: the flags of gemm_w8 (the fused MX kernel's rounding sequence; k-wave sums and epilogues shared)
+$(BUILD)/k_gemm_mx.o: turboinfer_amd/csrc/kernels/gemm_mx.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
 # wsynth_mx: scalar fp32 arithmetic that must match the host packer bit for bit (no contraction, no packed fp32)
 $(BUILD)/k_wsynth_mx.o: turboinfer_amd/csrc/kernels/wsynth_mx.hip $(HDRS)
 	@mkdir -p $(BUILD)

@@ -109,7 +109,8 @@ int ti_engine_set_stop(ti_engine* e, int32_t token);
  * (one gemm_w8_kernel launch per projection, or fused pieces with TI_GEMM_W8_ROWS=0); an fp16-weight engine
  * (bits 16) counts the same way (gemm_w16_kernel, or fused pieces with TI_GEMM_W16_ROWS=0).  A Q8_0 engine
  * (8 | TI_BITS_G32) and a Q4_1 engine (4 | TI_BITS_G32 | TI_BITS_AFF: gemm_w4a_kernel, TI_GEMM_W4A_ROWS) count the
- * chunks they run, like int4: up to TI_GEMM_MAX_ROWS rows each, 16 with the knob at 0. */
+ * chunks they run, like int4: up to TI_GEMM_MAX_ROWS rows each, 16 with the knob at 0.  So does an MXFP4 engine
+ * (4 | TI_BITS_G32 | TI_BITS_MX): 16 rows each, TI_GEMM_MAX_ROWS when it was created with ti_gemm_set_mx_rows' switch on. */
 int ti_engine_counters(ti_engine* e, uint64_t* decode_steps, uint64_t* prefill_chunks);
 /* The graph cache since creation: graphs captured into it (a step or verify graph the cache did not hold), and
  * graphs dropped from it (a setter or a grown buffer changed something they bake in).  Two calls between which
@@ -434,7 +435,8 @@ int ti_engine_generate_lookahead_sampled(ti_engine* e, int stream, const int32_t
  * 2 tokens) run the last token as a prefill row too, and their first token comes from the final
  * rms_norm + lm_head on that row (env TI_PREFILL_LOGITS=0: a decode step instead).
  * Default: TI_GEMM_MAX_ROWS (int4, INT8, Q8_0, Q4_1 and fp16 weights; 16 where the format's rows route is off:
- * TI_GEMM_W8_ROWS=0, TI_GEMM_W16_ROWS=0, TI_GEMM_W4A_ROWS=0); 0 = off. */
+ * TI_GEMM_W8_ROWS=0, TI_GEMM_W16_ROWS=0, TI_GEMM_W4A_ROWS=0; MXFP4 weights: 16, TI_GEMM_MAX_ROWS on an engine
+ * created while ti_gemm_set_mx_rows' switch was on); 0 = off. */
 int ti_engine_set_prefill(ti_engine* e, int rows);
 /* The attention entry point (ti_hip.h) a prompt chunk of `rows` rows takes on this engine, as a label
  * in the style of ti_gemm_kernel_name: "ti_attn_prefill" / "ti_attn_prefill_f8" (row-major chunks: up

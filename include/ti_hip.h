@@ -375,6 +375,23 @@ int ti_gemm_w16_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* g
  * TI_ERR_UNSUPPORTED when ti_gemm_w4a_rows is 0.  ti_gemm_max_rows keeps its values. */
 int ti_gemm_w4a_rows(int M, int N, int K);
 int ti_gemm_w4a_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
+/* MXFP4 weights (4 | TI_BITS_G32 | TI_BITS_MX) above 16 rows, behind one process-wide switch that is OFF by default.
+ * ti_gemm_set_mx_rows(on): sets the switch (on != 0) and returns its previous value (0 / 1); its initial value is
+ * the environment variable TI_GEMM_MX_ROWS, read once, default 0.  ti_gemm_wq_a16 reads the switch at every call; a
+ * ti_engine reads it once, in ti_engine_create, and keeps that answer (its prompt chunks and buffers are sized by it).
+ * While the switch is on, ti_gemm_wq_a16 with TI_X_F16 rows and 17 <= M <= TI_GEMM_MAX_ROWS runs gemm_mx_kernel: one
+ * launch on the tiles and e8m0 scale bytes of ti_wpack_mx_host as they are, the fused kernel's arithmetic (per
+ * 32-block one MFMA sum of x v from zero, acc = fmaf(2^(e - 127), sum, acc) in k order; the k-waves summed in fixed
+ * order, so a second launch gives the same bits), every epilogue kind, any M in the range, under gemm_w8_kernel's
+ * conditions (K % 128 == 0, K <= 65535, N % 16 == 0; tiles, x and out 16-byte aligned, ldx % 8 == 0, ldo % 4 == 0)
+ * with scales 4-byte aligned.  Nothing is refused because of this route: a call it cannot serve (unaligned operands,
+ * TI_X_F32 / TI_X_F32_RMSNORM rows) and every call while the switch is off runs 16-row pieces of the fused kernel.
+ * ti_gemm_mx_rows: 1 when an M x N x K MXFP4 call with aligned TI_X_F16 rows takes gemm_mx_kernel now, 0 otherwise.
+ * ti_gemm_mx_plan: the instance such a call launches, in ti_gemm_w8_plan's terms (*rb 2 or 4).
+ * TI_ERR_UNSUPPORTED when ti_gemm_mx_rows is 0.  ti_gemm_max_rows keeps its values. */
+int ti_gemm_set_mx_rows(int on);
+int ti_gemm_mx_rows(int M, int N, int K);
+int ti_gemm_mx_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid);
 /* One-time kernel attribute setup; call before capturing ti_gemm_wq_a16 into a graph. */
 int ti_gemm_prepare(void);
 

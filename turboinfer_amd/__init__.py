@@ -175,6 +175,7 @@ EXPORTED = [
     "ti_engine_serve_requests_guided", "ti_engine_graph_counters",
     "ti_gemm_w8_rows", "ti_gemm_w8_plan", "ti_gemm_w8_rows_for", "ti_gemm_w8_plan_for",
     "ti_gemm_w16_rows", "ti_gemm_w16_plan", "ti_gemm_w4a_rows", "ti_gemm_w4a_plan",
+    "ti_gemm_set_mx_rows", "ti_gemm_mx_rows", "ti_gemm_mx_plan",
 ]
 
 _lib = None
@@ -232,6 +233,10 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_gemm_w4a_rows"):   # (older TI_LIB builds in A/B runs lack the Q4_1 rows kernel)
             L.ti_gemm_w4a_rows.argtypes = [i32, i32, i32]
             L.ti_gemm_w4a_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
+        if hasattr(L, "ti_gemm_mx_rows"):   # (older TI_LIB builds in A/B runs lack the MXFP4 rows kernel)
+            L.ti_gemm_set_mx_rows.argtypes = [i32]
+            L.ti_gemm_mx_rows.argtypes = [i32, i32, i32]
+            L.ti_gemm_mx_plan.argtypes = [i32, i32, i32] + [C.POINTER(C.c_int)] * 4
         L.ti_rmsnorm_f16.argtypes = [vp, i32, vp, f32, vp, i32, i32, i32, vp]
         L.ti_rmsnorm_f16_packed.argtypes = [vp, i32, vp, f32, vp, i32, i32, vp]
         L.ti_attn_workspace_bytes.argtypes = [i32, i32, i32, i32]
@@ -488,6 +493,20 @@ def gemm_w4a_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
     """(rb, tpw, kwaves, grid) of the gemm_w4a_kernel instance a Q4_1 M x N x K call launches."""
     v = [C.c_int() for _ in range(4)]
     check(lib().ti_gemm_w4a_plan(M, N, K, *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def gemm_set_mx_rows(on: bool) -> bool:
+    """Turn the process-wide MXFP4 rows route on or off (off by default; TI_GEMM_MX_ROWS sets the initial value) and
+    return the previous setting.  On: an MXFP4 (4 | BITS_G32 | BITS_MX) call with aligned fp16 rows and 17 ..
+    GEMM_MAX_ROWS rows takes gemm_mx_kernel, and an Engine created from now on prefills in GEMM_MAX_ROWS-row chunks."""
+    return bool(lib().ti_gemm_set_mx_rows(1 if on else 0))
+
+
+def gemm_mx_plan(M: int, N: int, K: int) -> tuple[int, int, int, int]:
+    """(rb, tpw, kwaves, grid) of the gemm_mx_kernel instance an MXFP4 M x N x K call launches (the route on)."""
+    v = [C.c_int() for _ in range(4)]
+    check(lib().ti_gemm_mx_plan(M, N, K, *[C.byref(x) for x in v]))
     return tuple(x.value for x in v)
 
 

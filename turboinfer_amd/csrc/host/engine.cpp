@@ -192,8 +192,15 @@ int ti_engine_create(const ti_engine_config* cfg, ti_engine** out) {
     if (const char* env = getenv("TI_ATTN_PART")) e->part_on = atoi(env) != 0;
     e->splits_max = e->splits_for(1);
     // int4 (also group-32): the tile GEMM; INT8 (also group-32): gemm_w8_kernel; fp16 weights: gemm_w16_kernel;
-    // Q4_1 (affine group-32): gemm_w4a_kernel
-    e->pf_rows = chunk_rows_max(c);
+    // Q4_1 (affine group-32): gemm_w4a_kernel; MXFP4: gemm_mx_kernel behind ti_gemm_set_mx_rows' switch.
+    // The switch is sampled here, where pf_rows, rows_cap and xn are sized, and the answer is kept for the engine's
+    // lifetime; ti_gemm_wq_a16 reads the switch at every call.  Both mismatches stay correct.  Sampled on, switch
+    // later off: gemm_rows finds ti_gemm_mx_rows == 0 and takes the fused-piece branch (16 normalised rows per
+    // call).  Sampled off: chunks and normalised rows stay at 16 per call; fp16 rows (O, down of a batched step)
+    // reach ti_gemm_wq_a16 whole, as they always did, and go whichever way the switch says at that call -- the
+    // buffers hold max_batch rows either way.
+    e->mx_rows = mx_rows_now(c);
+    e->pf_rows = chunk_rows_max(c, e->mx_rows);
     e->rows_cap = std::max(B, e->pf_rows);
     const int R = e->rows_cap;
     const int Rp = (R + 15) / 16 * 16;   // packed operands hold whole 16-row blocks
@@ -564,7 +571,7 @@ int ti_engine_prefill_attn_name(ti_engine* e, int rows, char* buf, int len) {
 }
 
 int ti_engine_set_prefill(ti_engine* e, int rows) {
-  if (!e || e->c.compat || rows < 0 || rows > e->rows_cap || (rows > 0 && rows > chunk_rows_max(e->c)))
+  if (!e || e->c.compat || rows < 0 || rows > e->rows_cap || (rows > 0 && rows > chunk_rows_max(e->c, e->mx_rows)))
     return ti_set_error(TI_ERR_ARG, "ti_engine_set_prefill: rows %d", rows);
   DeviceScope bind_(e);
   e->pf_rows = rows;

@@ -133,6 +133,7 @@ struct ti_engine {
   // as rows of the batched path, sharing that stream's KV cache (stride 0)
   int pf_rows = 0;             // 0 = off (prompts consumed one token per decode step)
   int rows_cap = 0;            // R = max(max_batch, pf_rows): rows the step buffers hold
+  bool mx_rows = false;        // MXFP4 engine: ti_gemm_set_mx_rows' switch as ti_engine_create found it (kept for life)
   int32_t* pf_ones = nullptr;  // [pf_rows] 1
   int32_t* pf_zero = nullptr;  // [1] 0
   int32_t* pf_base = nullptr;  // [pf_rows] positions of the chunk's rows
@@ -344,7 +345,8 @@ bool packed_rows(const ti_engine* e, int M);
 // rows / tile kernels, INT8 group-128 and group-32 (Q8_0 blocks) gemm_w8_kernel (ti_gemm_w8_rows_for: off
 // with TI_GEMM_W8_ROWS=0), fp16 weights gemm_w16_kernel (ti_gemm_w16_rows: off with TI_GEMM_W16_ROWS=0); the
 // Q4_1 (affine group-32) gemm_w4a_kernel (ti_gemm_w4a_rows: off with TI_GEMM_W4A_ROWS=0); the largest prompt
-// chunk.  Everything else (compat engines) runs 16-row fused pieces.
+// chunk; MXFP4 gemm_mx_kernel on an engine created while ti_gemm_set_mx_rows' switch was on (ti_engine::mx_rows,
+// passed in as `mx`).  Everything else (compat engines) runs 16-row fused pieces.
 inline bool w8_rows(const ti_engine_config& c) {
   return (c.bits & ~TI_BITS_G32) == 8 && ti_gemm_w8_rows_for(c.bits, 17, 16, 128) != 0;
 }
@@ -352,8 +354,11 @@ inline bool w16_rows(const ti_engine_config& c) { return c.bits == 16 && ti_gemm
 inline bool w4a_rows(const ti_engine_config& c) {
   return c.bits == (4 | TI_BITS_G32 | TI_BITS_AFF) && ti_gemm_w4a_rows(17, 16, 128) != 0;
 }
-inline int chunk_rows_max(const ti_engine_config& c) {
-  return (c.bits & ~TI_BITS_G32) == 4 || w8_rows(c) || w16_rows(c) || w4a_rows(c) ? TI_GEMM_MAX_ROWS : 16;
+inline bool mx_rows_now(const ti_engine_config& c) {   // (the switch at this moment: ti_engine_create samples it)
+  return c.bits == (4 | TI_BITS_G32 | TI_BITS_MX) && ti_gemm_mx_rows(17, 16, 128) != 0;
+}
+inline int chunk_rows_max(const ti_engine_config& c, bool mx = false) {
+  return (c.bits & ~TI_BITS_G32) == 4 || w8_rows(c) || w16_rows(c) || w4a_rows(c) || mx ? TI_GEMM_MAX_ROWS : 16;
 }
 int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind, int ldx, const float* nw,
               const ti_epilogue& epi, size_t out_elem, bool last_gets_ctr);

@@ -13,7 +13,7 @@ bool packed_rows(const ti_engine* e, int M) { return ti_gemm_packed_rows(e->c.bi
 // holds, or -- int4, when the rows do not fit -- rms_norm into fp16 rows once (e->xn) and
 // the batched-rows kernel in chunks of TI_GEMM_MAX_ROWS; INT8 (group 128, and group-32 Q8_0 blocks) above
 // 16 rows the same way with row-major fp16 rows through gemm_w8_kernel, fp16 weights through gemm_w16_kernel,
-// Q4_1 (affine group-32) through gemm_w4a_kernel.
+// Q4_1 (affine group-32) through gemm_w4a_kernel, MXFP4 (an engine created with the switch on) through gemm_mx_kernel.
 // Graph-capturable.
 int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind, int ldx, const float* nw,
               const ti_epilogue& epi, size_t out_elem, bool last_gets_ctr) {
@@ -34,9 +34,10 @@ int gemm_rows(ti_engine* e, const DevLinear& W, int M, const void* x, int x_kind
   } else if (M > 16 && e->xn && (x_kind == TI_X_F32_RMSNORM || x_kind == TI_X_F16) &&
              ((w8_rows(c) && ti_gemm_w8_rows_for(c.bits, std::min(M, TI_GEMM_MAX_ROWS), W.N, W.K)) ||
               (w16_rows(c) && ti_gemm_w16_rows(std::min(M, TI_GEMM_MAX_ROWS), W.N, W.K)) ||
-              (w4a_rows(c) && ti_gemm_w4a_rows(std::min(M, TI_GEMM_MAX_ROWS), W.N, W.K)))) {
-    // INT8 / fp16-weight / Q4_1 rows above 16: fp16 rows (normalised once), gemm_w8_kernel / gemm_w16_kernel /
-    // gemm_w4a_kernel in chunks of TI_GEMM_MAX_ROWS
+              (w4a_rows(c) && ti_gemm_w4a_rows(std::min(M, TI_GEMM_MAX_ROWS), W.N, W.K)) ||
+              (e->mx_rows && ti_gemm_mx_rows(std::min(M, TI_GEMM_MAX_ROWS), W.N, W.K)))) {
+    // INT8 / fp16-weight / Q4_1 / MXFP4 rows above 16: fp16 rows (normalised once), gemm_w8_kernel /
+    // gemm_w16_kernel / gemm_w4a_kernel / gemm_mx_kernel in chunks of TI_GEMM_MAX_ROWS
     if (x_kind == TI_X_F32_RMSNORM) {
       TI_TRY(ti_rmsnorm_f16(static_cast<const float*>(x), ldx, nw, c.eps, e->xn, W.K, M, W.K, e->s));
       x = e->xn;
@@ -406,7 +407,7 @@ PfAttn prefill_attn_route(const ti_engine* e, int rows) {
 // The prompt chunk: ti_engine_set_prefill's rows, or, when that is 0 (prompts consumed by decode steps), the
 // chunk of the entry points that prefill regardless (serve, score, lookahead, share_prefix).
 int prefill_chunk_rows(const ti_engine* e) {
-  return e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, chunk_rows_max(e->c));
+  return e->pf_rows > 0 ? e->pf_rows : std::min(e->rows_cap, chunk_rows_max(e->c, e->mx_rows));
 }
 
 // Prefill (reference forward_pass, inference_engine.cpp:1429-1491, with the KV kept): prompt

@@ -1,6 +1,6 @@
 // gemm_shared.hpp -- what the GEMM kernels of gemv.hip (int4 tile kernel), gemm_w8.hip (INT8 rows
-// kernel), gemm_w16.hip (fp16-weight rows kernel) and gemm_w4a.hip (Q4_1 rows kernel) have in common and is
-// independent of the weight format: the launch arguments, the swizzled
+// kernel), gemm_w16.hip (fp16-weight rows kernel), gemm_w4a.hip (Q4_1 rows kernel) and gemm_mx.hip (MXFP4 rows
+// kernel) have in common and is independent of the weight format: the launch arguments, the swizzled
 // activation image in LDS, the staged epilogue of a 64 x 16 output block.
 #pragma once
 #include "common.hpp"
@@ -181,5 +181,16 @@ bool w4a_rows_on();   // TI_GEMM_W4A_ROWS (0: the route is off)
 W4aPlan w4a_plan(int M, int N, int K, int cus);
 int w4a_prepare();    // dynamic-LDS cap of every instance (ti_gemm_prepare)
 int launch_w4a(const GemvArgs& a, const W4aPlan& p, hipStream_t s);
+
+// ------------------------------------------------------------ gemm_mx.hip (MXFP4 rows kernel), host side
+// The instance of gemm_mx_kernel a call takes, in W8Plan's terms.
+struct MxPlan {
+  int rb, tpw, kw, n_cb, n_rb, grid, lds;
+};
+bool mx_rows_on();        // the route's switch: TI_GEMM_MX_ROWS at first use (default 0: off), then mx_rows_set
+int mx_rows_set(int on);  // ti_gemm_set_mx_rows: sets the switch, returns its previous value
+MxPlan mx_plan(int M, int N, int K, int cus);
+int mx_prepare();         // dynamic-LDS cap of every instance (ti_gemm_prepare)
+int launch_mx(const GemvArgs& a, const MxPlan& p, hipStream_t s);
 
 }  // namespace ti

@@ -1978,6 +1978,7 @@ extern "C" int ti_gemm_prepare(void) {
   if (const int rc = w8_prepare()) return rc;
   if (const int rc = w16_prepare()) return rc;
   if (const int rc = w4a_prepare()) return rc;
+  if (const int rc = mx_prepare()) return rc;
   g_prepared.fetch_or(bit, std::memory_order_acq_rel);
   return TI_OK;
 }
@@ -2081,6 +2082,29 @@ extern "C" int ti_gemm_w4a_plan(int M, int N, int K, int* rb, int* tpw, int* kwa
   *grid = p.grid;
   return TI_OK;
 }
+// MXFP4 (4 | TI_BITS_G32 | TI_BITS_MX) fp16 rows above 16: gemm_mx_kernel (gemm_mx.hip) while the process-wide
+// switch is on (ti_gemm_set_mx_rows; initially TI_GEMM_MX_ROWS, default 0), read at every call; off: 16-row fused
+// pieces.
+static bool mx_route(int bits, int x_kind, int M) {
+  return bits == (4 | TI_BITS_G32 | TI_BITS_MX) && x_kind == TI_X_F16 && M > 16 && M <= TI_GEMM_MAX_ROWS &&
+         ti::mx_rows_on();
+}
+extern "C" int ti_gemm_set_mx_rows(int on) { return ti::mx_rows_set(on); }
+extern "C" int ti_gemm_mx_rows(int M, int N, int K) {
+  return mx_route(4 | TI_BITS_G32 | TI_BITS_MX, TI_X_F16, M) && N >= 16 && !(N & 15) && K >= 128 && !(K & 127) &&
+                 K <= 0xffff ? 1 : 0;
+}
+extern "C" int ti_gemm_mx_plan(int M, int N, int K, int* rb, int* tpw, int* kwaves, int* grid) {
+  if (!rb || !tpw || !kwaves || !grid) return ti_set_error(TI_ERR_ARG, "ti_gemm_mx_plan: null pointer");
+  if (!ti_gemm_mx_rows(M, N, K))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_mx_plan: M=%d N=%d K=%d is not a gemm_mx_kernel call", M, N, K);
+  const ti::MxPlan p = ti::mx_plan(M, N, K, query_cus());
+  *rb = p.rb;
+  *tpw = p.tpw;
+  *kwaves = p.kw;
+  *grid = p.grid;
+  return TI_OK;
+}
 extern "C" int ti_gemm_packed_rows(int bits, int M) { return bits == 4 && M > 16 && M < ti::tile_rows() ? 1 : 0; }
 extern "C" int ti_gemm_packed_rows_for(int bits, int M, int N, int K) {
   (void)K;
@@ -2162,7 +2186,8 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
                         "or TI_BITS_MX for 4 | G32; got %d)", bits);
   // group-32: int4 fp16 rows from tile_rows() on run on the tile kernel, everything else on the
   // fused kernel (more than 16 rows: in 16-row pieces, below); affine blocks on the fused kernel and, fp16 rows
-  // above 16, on gemm_w4a_kernel (g32_w4a below)
+  // above 16, on gemm_w4a_kernel (g32_w4a below); MXFP4 blocks the same way on gemm_mx_kernel (g32_mx) once its
+  // switch is on
   const bool g32_tile = g32 && !aff && !mx && bits == 4 && x_kind == TI_X_F16 && M >= tile_rows() && !epi->out_packed;
   // group-32 int4 fp16 rows 17..64: the batched-rows kernel (TI_GEMM_G32_ROWS=0: fused pieces, A/B knob)
   const bool g32_rowsk = g32 && !aff && !mx && bits == 4 && x_kind == TI_X_F16 && M > 16 && M < tile_rows() &&
@@ -2238,7 +2263,11 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
   // as above, the scale / minimum pairs as dwords), else the fused pieces below
   const bool g32_w4a = aff && w4a_route(bits | TI_BITS_G32 | TI_BITS_AFF, x_kind, M) && w8_vec && !((uintptr_t)scales & 3) &&
                        !epi->out_packed && !fold_out && !fold_in;
-  if (g32 && !g32_tile && !g32_rowsk && !g32_w8 && !g32_w4a && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
+  // MXFP4 fp16 rows above 16, the switch on: gemm_mx_kernel where it can serve the call (vector accesses as above,
+  // the scale bytes as dwords; folds are refused for MX above), else the fused pieces below
+  const bool g32_mx = mx && mx_route(bits | TI_BITS_G32 | TI_BITS_MX, x_kind, M) && w8_vec && !((uintptr_t)scales & 3) &&
+                      !epi->out_packed && !fold_out && !fold_in;
+  if (g32 && !g32_tile && !g32_rowsk && !g32_w8 && !g32_w4a && !g32_mx && M > g32_rows) {   // pieces of g32_rows rows through the fused kernel
     if (x_kind == TI_X_ATTN_SPLITS || x_kind == TI_X_F16_FOLDED || epi->out_packed)
       return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: group-32 rows > 16 need plain x rows");
     const size_t x_elem = x_kind == TI_X_F16 ? 2 : 4;
@@ -2307,6 +2336,27 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     a.epi = *epi;
     a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
     return launch_w4a(a, p, (hipStream_t)stream);
+  }
+  if (g32_mx) {   // MXFP4 rows above 16: gemm_mx_kernel
+    const MxPlan p = mx_plan(M, N, K, query_cus());
+    if (p.lds > 64 * 1024) {   // no-op once this device is prepared
+      const int rc = ti_gemm_prepare();
+      if (rc != TI_OK) return rc;
+    }
+    GemvArgs a;
+    a.tiles = (const u32x4*)tiles;
+    a.scales = scales;
+    a.x = x;
+    a.norm_w = norm_w;
+    a.eps = eps;
+    a.x_kind = x_kind;
+    a.ldx = ldx;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.epi = *epi;
+    a.stamp = ti_stamp_next(STAMP_TILE, p.grid);
+    return launch_mx(a, p, (hipStream_t)stream);
   }
   if (!g32 && w16_route(bits, x_kind, M)) {   // fp16-weight rows above 16: gemm_w16_kernel (nothing else serves them)
     if (epi->out_packed || fold_out || fold_in)
@@ -2421,7 +2471,7 @@ extern "C" int ti_epilogue_bytes(void) { return (int)sizeof(ti_epilogue); }
 
 // The kernel ti_gemm_wq_a16 launches for plain (not group-32) weights, for 8 | TI_BITS_G32 and for
 // 4 | TI_BITS_G32 | TI_BITS_AFF (aligned row-major calls): the same predicates as gemm_impl (use_batched, wide_tile,
-// tile_rows, rows_on, w8_route, w16_route, w4a_route).
+// tile_rows, rows_on, w8_route, w16_route, w4a_route, mx_route).
 // For bench / profile labels.
 extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len) {
   using namespace ti;
@@ -2443,8 +2493,9 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
     else snprintf(buf, (size_t)len, "gemv_wq_kernel<4,%d>", gemv_xmode(x_kind, M, K));
     return TI_OK;
   }
-  if (mxfp4) {   // the fused kernel's MX instance, more than 16 rows in pieces
-    snprintf(buf, (size_t)len, "gemv_mx_kernel<%d>", gemv_xmode(x_kind, M, K));
+  if (mxfp4) {   // gemm_mx_kernel while its switch is on, else the fused kernel's MX instance (more than 16 rows in pieces)
+    if (mx_route(bits, x_kind, M)) snprintf(buf, (size_t)len, "gemm_mx_kernel");
+    else snprintf(buf, (size_t)len, "gemv_mx_kernel<%d>", gemv_xmode(x_kind, M, K));
     return TI_OK;
   }
   if (q8_0) {   // the fused kernel, more than 16 rows in pieces
