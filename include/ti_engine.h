@@ -74,6 +74,14 @@ int ti_engine_set_tensor_q1(ti_engine* e, int slot, int layer, const uint8_t* q,
  * rms_norm hand-off and no fused QKV + attention launch (ti_engine_set_qkv_attn reports 0).  ti_engine_synth
  * and ti_engine_set_tensor quantize fp32 values per block by ti_wpack_host's rule. */
 int ti_engine_set_tensor_mx(ti_engine* e, int slot, int layer, const uint8_t* codes, const uint8_t* scales);
+/* Q4_K super-blocks (ggml's GGML_TYPE_Q4_K) kept exact on an engine with bits 4 | TI_BITS_G32 | TI_BITS_KQ (hidden,
+ * heads * head_dim and inter multiples of 256): q uint8 [K][N_src] (0..15), sc and m uint8 [K/32][N_src] (0..63), d and
+ * dmin fp16 [K/256][N_src], weight = (d * sc) * q - dmin * m (ti_wpack_kq_host; its argument errors).  Such an engine
+ * runs every projection on the fused kernel's Q4_K instance (gemv_kq_kernel): prompts and batched steps in pieces of
+ * up to 16 rows, no folded rms_norm hand-off and no fused QKV + attention launch (ti_engine_set_qkv_attn reports 0).
+ * ti_engine_set_tensor refuses fp32 linear weights on it; ti_engine_synth fills seeded random blocks. */
+int ti_engine_set_tensor_kq(ti_engine* e, int slot, int layer, const uint8_t* q, const uint8_t* sc, const uint8_t* m,
+                            const uint16_t* d, const uint16_t* dmin);
 /* Synthetic model of SURVEY 8(d) generated on the device (bit-identical to the oracle's
  * or_model_synth for the same seed / jitter). */
 int ti_engine_synth(ti_engine* e, uint64_t seed, float norm_jitter);

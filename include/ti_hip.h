@@ -145,6 +145,23 @@ int ti_wpack_q1_host(const uint8_t* q, const uint16_t* d, const uint16_t* m, int
  * NaN, 0 is below what e << 23 expresses as a normal fp32). */
 int ti_wpack_mx_host(const uint8_t* codes, const uint8_t* e, int K, int N_src, int N_total, int row_map,
                      int row_offset, void* tiles, uint8_t* scales);
+/* GGUF Q4_K super-blocks (ggml's block_q4_K): bits = 4 | TI_BITS_G32 | TI_BITS_KQ, K % 256 == 0.  256 consecutive
+ * weights of one output row share fp16 d and dmin; each of their eight 32-weight blocks j has 6-bit sc_j and m_j:
+ * weight = (d * sc_j) * q - dmin * m_j, q in 0..15 (both products are exact in fp32).
+ * Tiles: the group-32 int4 layout and k order above with the raw q per nibble.  Scales: one 16-byte entry per
+ * output row and super-block, [N/16][K/256][16 rows][16 B] behind the uint16_t* of the shared signatures (4.5 bits
+ * per weight with the tiles).  An entry as four little-endian 32-bit words w0..w3:
+ *   w0 = d | dmin << 16 (fp16 bits);
+ *   field f = 2 j + (0: sc_j, 1: m_j) sits at bits 6 f .. 6 f + 5 of the 96-bit string w1 | w2 << 32 | w3 << 64,
+ *   so the four (sc, m) pairs of the entry's first 128-k tile are its bits 0 .. 47, the second tile's 48 .. 95.
+ * Fused kernel only (gemv_kq_kernel; more rows than its LDS image holds run in pieces); no tile or rows GEMM, no
+ * packed rows, no folded rms_norm hand-off, no fused QKV + attention launch.  ti_wpack_host / ti_engine_set_tensor
+ * refuse these bits (ggml's Q4_K quantizer is a search); ti_wsynth_device fills seeded random blocks. */
+#define TI_BITS_KQ 512
+/* Exact Q4_K blocks: q uint8 [K][N_src] (0..15), sc and m uint8 [K/32][N_src] (0..63), d and dmin fp16
+ * [K/256][N_src]; rows mapped as in ti_wpack_host. */
+int ti_wpack_kq_host(const uint8_t* q, const uint8_t* sc, const uint8_t* m, const uint16_t* d, const uint16_t* dmin,
+                     int K, int N_src, int N_total, int row_map, int row_offset, void* tiles, uint8_t* scales);
 
 /* The synthetic model of SURVEY 8(d) generated straight into device tiles:
  * element (k, c) of tensor `tensor_id` = u(seed, tensor_id, k*N_src + c) * amp,

@@ -31,6 +31,7 @@ GEMM_MAX_ROWS = 1024                # TI_GEMM_MAX_ROWS (include/ti_hip.h)
 BITS_G32 = 32                       # TI_BITS_G32 (include/ti_hip.h): group-32 weights (GGUF Q4_0 / Q8_0)
 BITS_AFF = 64                       # TI_BITS_AFF: affine group-32 int4 (GGUF Q4_1), with BITS_G32 | 4
 BITS_MX = 256                       # TI_BITS_MX: MXFP4 blocks (e2m1 nibbles, one e8m0 scale per 32), with BITS_G32 | 4
+BITS_KQ = 512                       # TI_BITS_KQ: GGUF Q4_K super-blocks (256 weights, 6-bit block scales / minimums), with BITS_G32 | 4
 BITS_KV8 = 128                      # TI_BITS_KV8: e4m3 KV cache, OR-ed into an engine's bits (any weight format)
 GUIDE_CAP = 64                      # TI_GUIDE_CAP (include/ti_engine.h): guides an engine's library holds at once
 SCALE_GROUP, SCALE_TENSOR, SCALE_UNIT = 0, 1, 2
@@ -154,6 +155,7 @@ EXPORTED = [
     "ti_wpack_q_host", "ti_engine_set_tensor_q", "ti_sample_workspace_bytes", "ti_sample_device_ws",
     "ti_wpack_q1_host", "ti_engine_set_tensor_q1", "ti_epilogue_bytes",
     "ti_wpack_mx_host", "ti_engine_set_tensor_mx",
+    "ti_wpack_kq_host", "ti_engine_set_tensor_kq",
     "ti_sample_step_ws", "ti_hbm_calibrate", "ti_gemm_kernel_name",
     "ti_gemm_fold_partials", "ti_gemm_mb_plan", "ti_engine_set_stop", "ti_engine_counters",
     "ti_qkv_attn_partials", "ti_qkv_attn_part_o_elems", "ti_qkv_attn_part_ml_elems", "ti_engine_set_qkv_attn",
@@ -284,6 +286,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "ti_engine_set_tensor_mx"):
             L.ti_engine_set_tensor_mx.argtypes = [vp, i32, i32, vp, vp]
             L.ti_wpack_mx_host.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        if hasattr(L, "ti_engine_set_tensor_kq"):
+            L.ti_engine_set_tensor_kq.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+            L.ti_wpack_kq_host.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.ti_engine_synth.argtypes = [vp, u64, f32]
         L.ti_engine_fill_kv.argtypes = [vp, i32, i32, u64]
         L.ti_engine_generate.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp]
@@ -548,6 +553,25 @@ def wpack_mx(codes, e, n_total=None, row_map: int = ROWS_CONCAT, row_offset: int
     return tiles, scales
 
 
+def wpack_kq(q, sc, m, d, dmin, n_total=None, row_map: int = ROWS_CONCAT, row_offset: int = 0, tiles=None, scales=None):
+    """ti_wpack_kq_host: exact Q4_K super-blocks, q uint8 [K][N] (0..15), sc and m uint8 [K/32][N] (0..63), d and
+    dmin fp16 [K/256][N] (weight = d sc q - dmin m), into (tiles bytes, scale bytes [N/16][K/256][16][16]) of bits
+    4 | BITS_G32 | BITS_KQ (include/ti_hip.h has the 16-byte entry)."""
+    q, sc, m = (np.ascontiguousarray(a, np.uint8) for a in (q, sc, m))
+    d, dmin = (np.ascontiguousarray(a, np.float16).view(np.uint16) for a in (d, dmin))
+    K, N = q.shape
+    n_total = n_total or N
+    L = lib()
+    bits = 4 | BITS_G32 | BITS_KQ
+    if tiles is None:
+        tiles = np.zeros(L.ti_wpack_tile_bytes(bits, K, n_total), np.uint8)
+    if scales is None:
+        scales = np.zeros(L.ti_wpack_scale_bytes(bits, K, n_total), np.uint8)
+    check(L.ti_wpack_kq_host(_ptr(q), _ptr(sc), _ptr(m), _ptr(d), _ptr(dmin), K, N, n_total, row_map, row_offset,
+                             _ptr(tiles), _ptr(scales)))
+    return tiles, scales
+
+
 def packed_index(m, k, K):
     """TI_PACKED_INDEX (include/ti_hip.h): element (m, k) of a TI_X_F16_PACKED operand (numpy arrays ok)."""
     kt = K // 128
@@ -684,6 +708,14 @@ class Engine:
         ca = np.ascontiguousarray(codes, np.uint8)
         sa = np.ascontiguousarray(scales, np.uint8)
         check(lib().ti_engine_set_tensor_mx(self.h, slot, layer, ca.ctypes.data, sa.ctypes.data))
+
+    def set_tensor_kq(self, slot, layer, q, sc, m, d, dmin):
+        """Exact Q4_K super-blocks (engine bits 4 | BITS_G32 | BITS_KQ): q uint8 [K][N] (0..15), sc and m uint8
+        [K/32][N] (0..63), d and dmin fp16 [K/256][N]; weight = d sc q - dmin m."""
+        qa, sa, ma = (np.ascontiguousarray(a, np.uint8) for a in (q, sc, m))
+        da, na = (np.ascontiguousarray(a, np.float16).view(np.uint16) for a in (d, dmin))
+        check(lib().ti_engine_set_tensor_kq(self.h, slot, layer, qa.ctypes.data, sa.ctypes.data, ma.ctypes.data,
+                                            da.ctypes.data, na.ctypes.data))
 
     def set_tensor(self, slot, layer, data, scale_mode=SCALE_GROUP):
         a = np.ascontiguousarray(data, np.float32)

@@ -66,6 +66,28 @@ inline float half_to_float(uint16_t h) {
   return f;
 }
 
+/// One ggml block_q4_K { fp16 d, dmin; uint8_t scales[12]; uint8_t qs[128]; } (144 bytes, 256 weights) taken apart:
+/// the 6-bit sc_j, m_j of sub-block j by ggml's get_scale_min_k4, and q in k order (chunk c of 64 weights is
+/// qs[32 c .. 32 c + 31]: sub-block 2 c its low nibbles, 2 c + 1 its high ones).  The loader's dequantization and the
+/// engine's upload both go through this.
+struct Q4KBlock {
+  uint16_t d, dmin;
+  uint8_t sc[8], m[8], q[256];
+};
+inline Q4KBlock q4k_unpack(const uint8_t* b) {
+  Q4KBlock o;
+  std::memcpy(&o.d, b, 2);
+  std::memcpy(&o.dmin, b + 2, 2);
+  const uint8_t* s = b + 4;
+  for (int j = 0; j < 8; ++j) {
+    o.sc[j] = j < 4 ? s[j] & 63 : (s[j + 4] & 15) | ((s[j - 4] >> 6) << 4);
+    o.m[j] = j < 4 ? s[j + 4] & 63 : (s[j + 4] >> 4) | ((s[j] >> 6) << 4);
+    const uint8_t* qs = b + 16 + 32 * (j >> 1);
+    for (int l = 0; l < 32; ++l) o.q[32 * j + l] = (j & 1) ? qs[l] >> 4 : qs[l] & 15;
+  }
+  return o;
+}
+
 /// Elements as fp32, the reference's convert_dtype (tensor_engine.cpp:2218-2284): integer
 /// tensors are a raw value cast, fp16 is widened.
 inline std::vector<float> to_f32(const core::Tensor& t) {

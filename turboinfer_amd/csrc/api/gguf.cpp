@@ -13,6 +13,7 @@
 //   * tensor data starts at the first general.alignment (default 32) boundary after the
 //     tensor infos and tensor i sits at data_start + offset_i (the reference seeks each offset
 //     relative to where the previous read ended, :842, correct for the first tensor only);
+//   * Q4_K (type 12) super-blocks are dequantized to fp32 too and also kept raw beside the tensor (dequant_q4_k);
 //   * Q4_0, Q4_1, Q8_0 and MXFP4 (type 39) blocks are dequantized to fp32 (ggml's block formats: 32 weights per
 //     block, an fp16 scale d (and min m), y = (q - 8) d, q d + m, q d); the reference declares
 //     these types fp32 and reads the packed bytes as floats (:165-182, 817-829).  BF16 is
@@ -26,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "api_common.hpp"
 #include "turboinfer/model/model_loader.hpp"
 
 namespace turboinfer {
@@ -39,7 +41,7 @@ enum GgufValue : uint32_t {
   kU8 = 0, kI8 = 1, kU16 = 2, kI16 = 3, kU32 = 4, kI32 = 5, kF32 = 6, kBool = 7, kStr = 8, kArr = 9,
   kU64 = 10, kI64 = 11, kF64 = 12
 };
-enum GgmlType : uint32_t { kTF32 = 0, kTF16 = 1, kTQ4_0 = 2, kTQ4_1 = 3, kTQ8_0 = 8, kTBF16 = 30, kTMXFP4 = 39 };
+enum GgmlType : uint32_t { kTF32 = 0, kTF16 = 1, kTQ4_0 = 2, kTQ4_1 = 3, kTQ8_0 = 8, kTQ4_K = 12, kTBF16 = 30, kTMXFP4 = 39 };
 
 struct Reader {
   std::ifstream f;
@@ -170,6 +172,24 @@ void dequant_mxfp4(const uint8_t* b, size_t nblk, float* y) {
   }
 }
 
+// Q4_K (GGML_TYPE_Q4_K, 144 bytes per 256 weights; api::q4k_unpack takes a block apart).  The fp32 value is
+// fl(fl(d sc) q) - fl(dmin m): both products of a half and a 6-bit integer are exact, so two roundings.  The product
+// and the difference are separate statements and the Makefile builds this directory with -ffp-contract=off, so no
+// fused multiply-subtract replaces them.
+void dequant_q4_k(const uint8_t* b, size_t nblk, float* y) {
+  for (size_t i = 0; i < nblk; ++i, b += 144, y += 256) {
+    const api::Q4KBlock k = api::q4k_unpack(b);
+    const float d = half_to_float(k.d), dmin = half_to_float(k.dmin);
+    for (int j = 0; j < 8; ++j) {
+      const float dsc = d * (float)k.sc[j], dm = dmin * (float)k.m[j];
+      for (int l = 0; l < 32; ++l) {
+        const float t = dsc * (float)k.q[32 * j + l];
+        y[32 * j + l] = t - dm;
+      }
+    }
+  }
+}
+
 struct Info {
   std::string name;
   std::vector<size_t> dims;   // reversed: row-major
@@ -184,9 +204,12 @@ size_t stored_bytes(uint32_t type, size_t n, const std::string& name) {
     case kTQ4_0: case kTQ4_1: case kTQ8_0: case kTMXFP4:
       if (n % 32) throw std::runtime_error("GGUF: tensor " + name + " is not a whole number of 32-weight blocks");
       return n / 32 * (type == kTQ4_0 ? 18 : type == kTQ4_1 ? 20 : type == kTMXFP4 ? 17 : 34);
+    case kTQ4_K:
+      if (n % 256) throw std::runtime_error("GGUF: tensor " + name + " is not a whole number of 256-weight super-blocks");
+      return n / 256 * 144;
     default:
       throw std::runtime_error("GGUF: tensor " + name + " has unsupported ggml type " + std::to_string(type) +
-                               " (supported: F32, F16, BF16, Q4_0, Q4_1, Q8_0, MXFP4)");
+                               " (supported: F32, F16, BF16, Q4_0, Q4_1, Q8_0, MXFP4, Q4_K)");
   }
 }
 
@@ -268,6 +291,16 @@ ModelData ModelLoader::load_gguf(const std::string& file_path) {
     else if (t.type == kTQ4_1) dequant_q4_1(raw.data(), n / 32, y);
     else if (t.type == kTQ8_0) dequant_q8_0(raw.data(), n / 32, y);
     else if (t.type == kTMXFP4) dequant_mxfp4(raw.data(), n / 32, y);
+    else if (t.type == kTQ4_K) {
+      // The 6-bit fields cannot be recovered from fp32 values (a sub-block need not hold q = 0), so the raw blocks
+      // travel with the tensor as <name>.ggml_q4_k, kUInt8 {n_blocks, 144}: what the engine uploads.
+      if (t.dims.back() % 256)
+        throw std::runtime_error("GGUF: Q4_K tensor " + t.name + " has rows that are not whole 256-weight super-blocks");
+      dequant_q4_k(raw.data(), n / 256, y);
+      core::Tensor blocks(core::TensorShape({n / 256, (size_t)144}), core::DataType::kUInt8);
+      std::memcpy(blocks.data(), raw.data(), bytes);
+      md.add_tensor(t.name + ".ggml_q4_k", std::move(blocks));
+    }
     else if (t.type == kTBF16)
       for (size_t i = 0; i < n; ++i) {
         const uint32_t bits = (uint32_t)(raw[2 * i] | (raw[2 * i + 1] << 8)) << 16;

@@ -216,17 +216,22 @@ ModelData from_gguf_names(const ModelData& g) {
   const core::Tensor& emb = need("token_embd.weight");
   if (m.metadata().vocab_size == 0 && emb.shape().ndim() == 2) m.metadata().vocab_size = emb.shape().size(0);
   m.add_tensor("norm.weight", need("output_norm.weight"));
-  const core::Tensor* out = g.get_tensor("output.weight");
-  m.add_tensor("lm_head.weight", transposed_f32(out ? *out : need("token_embd.weight")));
+  // a linear weight [out][in] -> [in][out]; the raw Q4_K super-blocks gguf.cpp put beside a type-12 tensor keep the
+  // file's order ([out][in / 256] blocks) under the new name
+  auto linear = [&](const std::string& to, const std::string& from) {
+    m.add_tensor(to, transposed_f32(need(from)));
+    if (const core::Tensor* raw = g.get_tensor(from + ".ggml_q4_k")) m.add_tensor(to + ".ggml_q4_k", *raw);
+  };
+  linear("lm_head.weight", g.get_tensor("output.weight") ? "output.weight" : "token_embd.weight");
   for (size_t l = 0; l < g.metadata().num_layers; ++l) {
     const std::string b = "blk." + std::to_string(l) + ".", r = "layers." + std::to_string(l) + ".";
-    m.add_tensor(r + "attention.q_proj.weight", transposed_f32(need(b + "attn_q.weight")));
-    m.add_tensor(r + "attention.k_proj.weight", transposed_f32(need(b + "attn_k.weight")));
-    m.add_tensor(r + "attention.v_proj.weight", transposed_f32(need(b + "attn_v.weight")));
-    m.add_tensor(r + "attention.o_proj.weight", transposed_f32(need(b + "attn_output.weight")));
-    m.add_tensor(r + "feed_forward.w3.weight", transposed_f32(need(b + "ffn_gate.weight")));
-    m.add_tensor(r + "feed_forward.w1.weight", transposed_f32(need(b + "ffn_up.weight")));
-    m.add_tensor(r + "feed_forward.w2.weight", transposed_f32(need(b + "ffn_down.weight")));
+    linear(r + "attention.q_proj.weight", b + "attn_q.weight");
+    linear(r + "attention.k_proj.weight", b + "attn_k.weight");
+    linear(r + "attention.v_proj.weight", b + "attn_v.weight");
+    linear(r + "attention.o_proj.weight", b + "attn_output.weight");
+    linear(r + "feed_forward.w3.weight", b + "ffn_gate.weight");
+    linear(r + "feed_forward.w1.weight", b + "ffn_up.weight");
+    linear(r + "feed_forward.w2.weight", b + "ffn_down.weight");
     m.add_tensor(r + "attention_norm.weight", need(b + "attn_norm.weight"));
     m.add_tensor(r + "ffn_norm.weight", need(b + "ffn_norm.weight"));
   }
@@ -409,6 +414,53 @@ class InferenceEngineImpl {
   };
   std::map<const core::Tensor*, Blocks> g32;
 
+  // Q4_K: the raw super-blocks ([N][K / 256][144 B], gguf.cpp) that came with each linear weight, for upload()
+  std::map<const core::Tensor*, const core::Tensor*> kq;
+
+  // every linear weight of a GGUF-read model came as Q4_K super-blocks along a K of whole super-blocks
+  bool all_kq(const ModelData& m, size_t L, size_t H, size_t qd, size_t kvd, size_t I, size_t V) {
+    kq.clear();
+    auto one = [&](const std::string& name, size_t K, size_t N) {
+      const core::Tensor *t = m.get_tensor(name), *raw = m.get_tensor(name + ".ggml_q4_k");
+      if (!t || !raw || K % 256 || t->shape().total_size() != K * N || raw->dtype() != core::DataType::kUInt8 ||
+          raw->shape().total_size() != K / 256 * N * 144)
+        return false;
+      kq[t] = raw;
+      return true;
+    };
+    bool ok = one("lm_head.weight", H, V);
+    for (size_t l = 0; l < L && ok; ++l) {
+      const std::string r = "layers." + std::to_string(l) + ".";
+      ok = one(r + "attention.q_proj.weight", H, qd) && one(r + "attention.k_proj.weight", H, kvd) &&
+           one(r + "attention.v_proj.weight", H, kvd) && one(r + "attention.o_proj.weight", qd, H) &&
+           one(r + "feed_forward.w3.weight", H, I) && one(r + "feed_forward.w1.weight", H, I) &&
+           one(r + "feed_forward.w2.weight", I, H);
+    }
+    if (!ok) kq.clear();
+    return ok;
+  }
+
+  // One linear weight's raw super-blocks ([N][K / 256] blocks) as ti_engine_set_tensor_kq takes them ([K][N] q,
+  // [K/32][N] sc and m, [K/256][N] d and dmin), through the loader's api::q4k_unpack.
+  void upload_kq(int slot, int layer, const core::Tensor& raw, size_t K, size_t N) {
+    std::vector<uint8_t> q(K * N), sc(K / 32 * N), mn(K / 32 * N);
+    std::vector<uint16_t> d(K / 256 * N), dmin(K / 256 * N);
+    const uint8_t* b = static_cast<const uint8_t*>(raw.data());
+    for (size_t n = 0; n < N; ++n)
+      for (size_t sb = 0; sb < K / 256; ++sb, b += 144) {
+        const api::Q4KBlock k = api::q4k_unpack(b);
+        d[sb * N + n] = k.d;
+        dmin[sb * N + n] = k.dmin;
+        for (size_t j = 0; j < 8; ++j) {
+          sc[(sb * 8 + j) * N + n] = k.sc[j];
+          mn[(sb * 8 + j) * N + n] = k.m[j];
+        }
+        for (size_t i = 0; i < 256; ++i) q[(sb * 256 + i) * N + n] = k.q[i];
+      }
+    check(ti_engine_set_tensor_kq(eng, slot, layer, q.data(), sc.data(), mn.data(), d.data(), dmin.data()),
+          "ti_engine_set_tensor_kq");
+  }
+
   static bool recover(const std::vector<float>& w, size_t K, size_t N, int bits, Blocks& b) {
     if (bits & TI_BITS_MX) return recover_mx(w, K, N, b.q, b.e);
     return (bits & TI_BITS_AFF) ? recover_q41(w, K, N, b.q, b.d, b.m)
@@ -442,6 +494,11 @@ class InferenceEngineImpl {
   }
 
   void upload(int slot, int layer, const core::Tensor& t, size_t K, size_t N, int bits) {
+    if (bits & TI_BITS_KQ) {   // (build() chose or accepted the bits because every linear weight is in kq)
+      const auto it = kq.find(&t);
+      if (it == kq.end()) throw std::runtime_error("InferenceEngine: no Q4_K super-blocks for slot " + std::to_string(slot));
+      return upload_kq(slot, layer, *it->second, K, N);
+    }
     if ((bits & TI_BITS_G32) && t.shape().total_size() == K * N) {   // exact blocks when the weight has them
       auto it = g32.find(&t);
       Blocks b;
@@ -526,7 +583,9 @@ class InferenceEngineImpl {
     cfg.rope_theta = md.rope_theta > 0.0f ? md.rope_theta : 10000.0f;
     cfg.eps = 1e-5f;
     const int bits = engine_option(md, "turboinfer.weight_bits", "TI_WEIGHT_BITS", 0);
-    cfg.bits = bits == 8 || bits == 16 || bits == (4 | TI_BITS_G32 | TI_BITS_MX) ? bits : 4;
+    // (Q4_K: ti_engine_synth's seeded random blocks; ti_engine_create refuses a shape that is not whole super-blocks)
+    cfg.bits = bits == 8 || bits == 16 || bits == (4 | TI_BITS_G32 | TI_BITS_MX) || bits == (4 | TI_BITS_G32 | TI_BITS_KQ)
+                   ? bits : 4;
     kv_bits = kv_bits_option(md);
     lookahead = lookahead_option(md, kv_bits);
     share_prefix = share_prefix_option(md, kv_bits);
@@ -580,6 +639,9 @@ class InferenceEngineImpl {
           if (x < -8.0f || x > 7.0f) bits = 8;
       } else if (gguf_src && q0) {   // Q4_0 / Q4_1 / Q8_0 checkpoint: keep its blocks
         const size_t kvd = k0 ? k0->shape().total_size() / H : H;
+        // Q4_K first: its 6-bit fields come from the raw blocks beside the tensors, never from the fp32 values
+        if (all_kq(m, L, H, H, kvd, I, V)) bits = 4 | TI_BITS_G32 | TI_BITS_KQ;
+        else
         // Order: Q4_0, Q4_1, MXFP4, Q8_0.  Q4_0 first, so a Q4_0 file stays Q4_0 (its blocks hold q = 5 or 7 times d,
         // which no e2m1 grid holds beside 8 d, so they would not pass as MX anyway); MXFP4 before Q8_0, because every MX
         // block is also integers of [-12, 12] times a power of two, i.e. a valid Q8_0 block.
@@ -589,11 +651,16 @@ class InferenceEngineImpl {
         else if (all_g32(m, L, H, H, kvd, I, V, 8 | TI_BITS_G32)) bits = 8 | TI_BITS_G32;
       }
     }
+    if (bits == (4 | TI_BITS_G32 | TI_BITS_KQ) && kq.empty() &&
+        !(gguf_src && q0 && all_kq(m, L, H, H, k0 ? k0->shape().total_size() / H : H, I, V)))
+      throw std::runtime_error("InferenceEngine: weight_bits 4 | 32 | 512 (Q4_K super-blocks) needs a GGUF model whose "
+                               "every linear weight is Q4_K with K % 256 == 0; fp32 weights are not quantized into it");
     if (bits != 4 && bits != 8 && bits != 16 && bits != (4 | TI_BITS_G32) && bits != (8 | TI_BITS_G32) &&
-        bits != (4 | TI_BITS_G32 | TI_BITS_AFF) && bits != (4 | TI_BITS_G32 | TI_BITS_MX))
+        bits != (4 | TI_BITS_G32 | TI_BITS_AFF) && bits != (4 | TI_BITS_G32 | TI_BITS_MX) &&
+        bits != (4 | TI_BITS_G32 | TI_BITS_KQ))
       throw std::runtime_error(
-          "InferenceEngine: weight_bits must be 4, 8, 16, 4 / 8 | 32 (group-32 blocks), 4 | 32 | 64 (Q4_1 blocks) or "
-          "4 | 32 | 256 (MXFP4 blocks)");
+          "InferenceEngine: weight_bits must be 4, 8, 16, 4 / 8 | 32 (group-32 blocks), 4 | 32 | 64 (Q4_1 blocks), "
+          "4 | 32 | 256 (MXFP4 blocks) or 4 | 32 | 512 (Q4_K super-blocks of a GGUF model)");
     cfg.vocab = (int)V;
     cfg.hidden = (int)H;
     cfg.layers = (int)L;
@@ -1085,8 +1152,8 @@ std::string InferenceEngine::performance_stats() const {
   if (im.total_time_ms > 0.0f)
     os << "  Average Tokens/Second: " << (im.total_tokens / (im.total_time_ms / 1000.0f)) << "\n";
   os << "  Peak Tokens/Second: " << im.peak_tps << "\n";
-  os << "  Device Memory: " << (memory_usage() / (1024.0 * 1024.0)) << " MB (weights " << (im.cfg.bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX))
-     << "-bit" << ((im.cfg.bits & TI_BITS_MX) ? " MXFP4 blocks" : (im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << (im.kv_bits == 8 ? ", fp8 KV, " : ", fp16 KV, ") << im.capacity
+  os << "  Device Memory: " << (memory_usage() / (1024.0 * 1024.0)) << " MB (weights " << (im.cfg.bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX | TI_BITS_KQ))
+     << "-bit" << ((im.cfg.bits & TI_BITS_KQ) ? " Q4_K super-blocks" : (im.cfg.bits & TI_BITS_MX) ? " MXFP4 blocks" : (im.cfg.bits & TI_BITS_AFF) ? " affine group-32 blocks" : (im.cfg.bits & TI_BITS_G32) ? " group-32 blocks" : "") << (im.kv_bits == 8 ? ", fp8 KV, " : ", fp16 KV, ") << im.capacity
      << " stream(s) x " << im.cfg.max_seq << " slots)\n";
   os << "  Mode: " << (im.compat ? "reference_compat (plumbing model)" : "llama decode") << "\n";
   return os.str();

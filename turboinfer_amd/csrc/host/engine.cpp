@@ -48,10 +48,14 @@ int validate(const ti_engine_config& c) {
   if (c.head_dim != 64 && c.head_dim != 128) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: head_dim %d", c.head_dim);
   const int wbits = c.bits & ~TI_BITS_KV8;   // the weight format; TI_BITS_KV8 goes with every one
   if (wbits != 4 && wbits != 8 && wbits != 16 && wbits != (4 | TI_BITS_G32) && wbits != (8 | TI_BITS_G32) &&
-      wbits != (4 | TI_BITS_G32 | TI_BITS_AFF) && wbits != (4 | TI_BITS_G32 | TI_BITS_MX))
+      wbits != (4 | TI_BITS_G32 | TI_BITS_AFF) && wbits != (4 | TI_BITS_G32 | TI_BITS_MX) &&
+      wbits != (4 | TI_BITS_G32 | TI_BITS_KQ))
     return ti_set_error(TI_ERR_ARG, "ti_engine_create: bits %d (4, 8, 16; 4 or 8 | TI_BITS_G32; 4 | TI_BITS_G32 | "
-                        "TI_BITS_AFF; 4 | TI_BITS_G32 | TI_BITS_MX; each | TI_BITS_KV8)", c.bits);
+                        "TI_BITS_AFF; 4 | TI_BITS_G32 | TI_BITS_MX; 4 | TI_BITS_G32 | TI_BITS_KQ; each | TI_BITS_KV8)", c.bits);
   const int qd = c.heads * c.head_dim, kvd = c.kv_heads * c.head_dim;
+  if ((wbits & TI_BITS_KQ) && (c.hidden % 256 || qd % 256 || c.inter % 256))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: Q4_K super-blocks (TI_BITS_KQ) need hidden, heads*head_dim "
+                        "and inter to be multiples of 256");
   if (c.hidden % 128 || qd % 128 || c.inter % 128)
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_create: hidden, heads*head_dim and inter must be multiples of 128");
   if (kvd % 16 || c.vocab % 16)
@@ -336,6 +340,8 @@ static int set_tensor_blocks(ti_engine* e, int slot, int layer, const void* q, c
   if (!(c.bits & TI_BITS_G32)) return ti_set_error(TI_ERR_ARG, "%s: engine bits %d lack TI_BITS_G32", fn, c.bits);
   if (c.bits & TI_BITS_MX)
     return ti_set_error(TI_ERR_ARG, "%s: engine bits %d hold MXFP4 blocks (ti_engine_set_tensor_mx)", fn, c.bits);
+  if (c.bits & TI_BITS_KQ)
+    return ti_set_error(TI_ERR_ARG, "%s: engine bits %d hold Q4_K super-blocks (ti_engine_set_tensor_kq)", fn, c.bits);
   if (((c.bits & TI_BITS_AFF) != 0) != (m != nullptr))
     return ti_set_error(TI_ERR_ARG, "%s: engine bits %d (%s blocks expected)", fn, c.bits,
                         (c.bits & TI_BITS_AFF) ? "affine Q4_1" : "Q4_0 / Q8_0");
@@ -377,6 +383,29 @@ int ti_engine_set_tensor_q1(ti_engine* e, int slot, int layer, const uint8_t* q,
   return set_tensor_blocks(e, slot, layer, q, d, m);
 }
 
+// The fused buffer a linear slot is part of, and where its rows go in it (null: the error is set).
+static DevLinear* linear_part(ti_engine* e, const char* fn, int slot, int layer, int* K, int* Nsrc, int* map, int* off) {
+  const ti_engine_config& c = e->c;
+  const int H = c.hidden, I = c.inter, V = c.vocab, qd = e->qd(), kvd = e->kvd();
+  if (layer < 0 || (slot <= TI_W_DOWN && layer >= c.layers)) {
+    ti_set_error(TI_ERR_ARG, "%s: layer %d", fn, layer);
+    return nullptr;
+  }
+  *map = TI_ROWS_CONCAT;
+  *off = 0;
+  switch (slot) {
+    case TI_W_Q: *K = H; *Nsrc = qd; return &e->layer[layer].qkv;
+    case TI_W_K: *K = H; *Nsrc = kvd; *off = qd; return &e->layer[layer].qkv;
+    case TI_W_V: *K = H; *Nsrc = kvd; *off = qd + kvd; return &e->layer[layer].qkv;
+    case TI_W_O: *K = qd; *Nsrc = H; return &e->layer[layer].o;
+    case TI_W_GATE: *K = H; *Nsrc = I; *map = TI_ROWS_INTERLEAVE8; return &e->layer[layer].gu;
+    case TI_W_UP: *K = H; *Nsrc = I; *map = TI_ROWS_INTERLEAVE8; *off = 8; return &e->layer[layer].gu;
+    case TI_W_DOWN: *K = I; *Nsrc = H; return &e->layer[layer].down;
+    case TI_W_LM_HEAD: *K = H; *Nsrc = V; return &e->lm;
+    default: ti_set_error(TI_ERR_ARG, "%s: slot %d is not a linear weight", fn, slot); return nullptr;
+  }
+}
+
 // Exact MXFP4 blocks (e2m1 codes, e8m0 block scales) onto a TI_BITS_MX engine: ti_wpack_mx_host into the fused
 // buffer of the slot, as set_tensor_blocks does for Q4_0 / Q4_1.
 int ti_engine_set_tensor_mx(ti_engine* e, int slot, int layer, const uint8_t* codes, const uint8_t* scales) {
@@ -385,21 +414,9 @@ int ti_engine_set_tensor_mx(ti_engine* e, int slot, int layer, const uint8_t* co
   DeviceScope bind_(e);
   const ti_engine_config& c = e->c;
   if (c.compat || !(c.bits & TI_BITS_MX)) return ti_set_error(TI_ERR_ARG, "%s: engine bits %d lack TI_BITS_MX", fn, c.bits);
-  if (layer < 0 || (slot <= TI_W_DOWN && layer >= c.layers)) return ti_set_error(TI_ERR_ARG, "%s: layer %d", fn, layer);
-  const int H = c.hidden, I = c.inter, V = c.vocab, qd = e->qd(), kvd = e->kvd();
-  DevLinear* L = nullptr;
   int K = 0, Nsrc = 0, map = TI_ROWS_CONCAT, off = 0;
-  switch (slot) {
-    case TI_W_Q: L = &e->layer[layer].qkv; K = H; Nsrc = qd; off = 0; break;
-    case TI_W_K: L = &e->layer[layer].qkv; K = H; Nsrc = kvd; off = qd; break;
-    case TI_W_V: L = &e->layer[layer].qkv; K = H; Nsrc = kvd; off = qd + kvd; break;
-    case TI_W_O: L = &e->layer[layer].o; K = qd; Nsrc = H; break;
-    case TI_W_GATE: L = &e->layer[layer].gu; K = H; Nsrc = I; map = TI_ROWS_INTERLEAVE8; off = 0; break;
-    case TI_W_UP: L = &e->layer[layer].gu; K = H; Nsrc = I; map = TI_ROWS_INTERLEAVE8; off = 8; break;
-    case TI_W_DOWN: L = &e->layer[layer].down; K = I; Nsrc = H; break;
-    case TI_W_LM_HEAD: L = &e->lm; K = H; Nsrc = V; break;
-    default: return ti_set_error(TI_ERR_ARG, "%s: slot %d is not a linear weight", fn, slot);
-  }
+  DevLinear* L = linear_part(e, fn, slot, layer, &K, &Nsrc, &map, &off);
+  if (!L) return TI_ERR_ARG;
   const size_t tb = ti_wpack_tile_bytes(c.bits, L->K, L->N), sb = ti_wpack_scale_bytes(c.bits, L->K, L->N);
   std::vector<uint8_t> th(tb), sh(sb);
   TI_TRY(ti_memcpy_d2h(th.data(), L->tiles, tb, e->s));
@@ -410,12 +427,33 @@ int ti_engine_set_tensor_mx(ti_engine* e, int slot, int layer, const uint8_t* co
   return ti_stream_sync(e->s);
 }
 
+// Exact Q4_K super-blocks onto a TI_BITS_KQ engine: ti_wpack_kq_host into the fused buffer of the slot.
+int ti_engine_set_tensor_kq(ti_engine* e, int slot, int layer, const uint8_t* q, const uint8_t* sc, const uint8_t* m,
+                            const uint16_t* d, const uint16_t* dmin) {
+  const char* fn = "ti_engine_set_tensor_kq";
+  if (!e || !q || !sc || !m || !d || !dmin) return ti_set_error(TI_ERR_ARG, "%s: null", fn);
+  DeviceScope bind_(e);
+  const ti_engine_config& c = e->c;
+  if (c.compat || !(c.bits & TI_BITS_KQ)) return ti_set_error(TI_ERR_ARG, "%s: engine bits %d lack TI_BITS_KQ", fn, c.bits);
+  int K = 0, Nsrc = 0, map = TI_ROWS_CONCAT, off = 0;
+  DevLinear* L = linear_part(e, fn, slot, layer, &K, &Nsrc, &map, &off);
+  if (!L) return TI_ERR_ARG;
+  const size_t tb = ti_wpack_tile_bytes(c.bits, L->K, L->N), sb = ti_wpack_scale_bytes(c.bits, L->K, L->N);
+  std::vector<uint8_t> th(tb), sh(sb);
+  TI_TRY(ti_memcpy_d2h(th.data(), L->tiles, tb, e->s));
+  TI_TRY(ti_memcpy_d2h(sh.data(), L->scales, sb, e->s));
+  TI_TRY(ti_wpack_kq_host(q, sc, m, d, dmin, K, Nsrc, L->N, map, off, th.data(), sh.data()));
+  TI_TRY(ti_memcpy_h2d(L->tiles, th.data(), tb, e->s));
+  TI_TRY(ti_memcpy_h2d(L->scales, sh.data(), sb, e->s));
+  return ti_stream_sync(e->s);
+}
+
 int ti_engine_synth(ti_engine* e, uint64_t seed, float norm_jitter) {
   if (!e) return ti_set_error(TI_ERR_ARG, "ti_engine_synth: null");
   DeviceScope bind_(e);
   const ti_engine_config& c = e->c;
   if (c.compat) return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_synth: compat engines take the reference model");
-  if ((c.bits & TI_BITS_G32) && !(c.bits & TI_BITS_MX))   // (MXFP4 engines: the synthetic values quantized per block)
+  if ((c.bits & TI_BITS_G32) && !(c.bits & (TI_BITS_MX | TI_BITS_KQ)))   // (MXFP4: the synthetic values quantized per block; Q4_K: seeded random blocks)
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_engine_synth: group-32 engines take their weights from ti_engine_set_tensor[_q]");
   const int H = c.hidden, I = c.inter, V = c.vocab, qd = e->qd(), kvd = e->kvd(), b = c.bits;
   for (int l = 0; l < c.layers; ++l) {

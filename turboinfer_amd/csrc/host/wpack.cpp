@@ -40,12 +40,13 @@ inline uint16_t to_half(float f) {
 
 extern "C" size_t ti_wpack_tile_bytes(int bits, int K, int N) {
   if (K <= 0 || N <= 0) return 0;
-  return (size_t)(N / 16) * (size_t)(K / 128) * 256u * (size_t)(bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX));
+  return (size_t)(N / 16) * (size_t)(K / 128) * 256u * (size_t)(bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX | TI_BITS_KQ));
 }
 
 extern "C" size_t ti_wpack_scale_bytes(int bits, int K, int N) {
   if (bits == 16 || K <= 0 || N <= 0) return 0;
   if (bits & TI_BITS_MX) return (size_t)(N / 16) * (size_t)(K / 128) * 64u;   // MXFP4: one e8m0 byte per block
+  if (bits & TI_BITS_KQ) return (size_t)(N / 16) * (size_t)(K / 256) * 256u;  // Q4_K: 16 bytes per row and super-block
   return (size_t)(N / 16) * (size_t)(K / 128) * 16u * sizeof(uint16_t) * ((bits & TI_BITS_G32) ? 4u : 1u) *
          ((bits & TI_BITS_AFF) ? 2u : 1u);   // affine group-32: the block minimums follow the scales
 }
@@ -130,8 +131,50 @@ extern "C" int ti_wpack_mx_host(const uint8_t* codes, const uint8_t* e, int K, i
   return TI_OK;
 }
 
+// Q4_K super-blocks (ti_hip.h): the raw q into the group-32 int4 tiles, and per output row and super-block one
+// 16-byte entry: d | dmin << 16, then the sixteen 6-bit fields sc_0, m_0, sc_1, m_1, .. in ascending bit order.
+extern "C" int ti_wpack_kq_host(const uint8_t* q, const uint8_t* sc, const uint8_t* m, const uint16_t* d,
+                                const uint16_t* dmin, int K, int N_src, int N_total, int row_map, int row_offset,
+                                void* tiles, uint8_t* scales) {
+  if (!q || !sc || !m || !d || !dmin || !tiles || !scales) return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: null pointer");
+  if (K <= 0 || (K & 255) || N_total <= 0 || (N_total & 15) || N_src <= 0)
+    return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: K %% 256 / N %% 16 (K=%d N_total=%d)", K, N_total);
+  if (row_map == TI_ROWS_INTERLEAVE8 && (N_src & 7)) return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: interleave needs N %% 8 == 0");
+  if (map_row(N_src - 1, row_map, row_offset) >= N_total || row_offset < 0)
+    return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: rows do not fit N_total");
+  const int KT = K / 128, KS = K / 256;
+  uint8_t* tb = static_cast<uint8_t*>(tiles);
+  int8_t col[128];
+  for (int c = 0; c < N_src; ++c) {
+    const int n = map_row(c, row_map, row_offset), nt = n >> 4, r = n & 15;
+    for (int g = 0; g < KT; ++g) {
+      for (int i = 0; i < 128; ++i) {
+        const int v = q[(size_t)(g * 128 + i) * N_src + c];
+        if (v > 15) return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: weight %d outside [0, 15]", v);
+        col[i] = (int8_t)(v - 8);   // (pack_row stores q + 8: the raw q)
+      }
+      pack_row(tb + ((size_t)nt * KT + g) * 1024, 4, true, r, col);
+    }
+    for (int sb = 0; sb < KS; ++sb) {
+      uint32_t w[4] = {(uint32_t)d[(size_t)sb * N_src + c] | ((uint32_t)dmin[(size_t)sb * N_src + c] << 16), 0u, 0u, 0u};
+      for (int f = 0; f < 16; ++f) {
+        const int v = (f & 1 ? m : sc)[(size_t)(sb * 8 + (f >> 1)) * N_src + c];
+        if (v > 63) return ti_set_error(TI_ERR_ARG, "ti_wpack_kq_host: 6-bit field %d outside [0, 63]", v);
+        const int bit = 6 * f;
+        w[1 + (bit >> 5)] |= (uint32_t)v << (bit & 31);
+        if ((bit & 31) > 26) w[2 + (bit >> 5)] |= (uint32_t)v >> (32 - (bit & 31));
+      }
+      std::memcpy(scales + (((size_t)nt * KS + sb) * 16 + r) * 16, w, 16);
+    }
+  }
+  return TI_OK;
+}
+
 extern "C" int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_src, int N_total, int bits, int row_map,
                                int row_offset, void* tiles, uint16_t* scales) {
+  if (bits & (TI_BITS_KQ | TI_BITS_MX))
+    return ti_set_error(TI_ERR_ARG, "ti_wpack_q_host: bits %d hold %s blocks (ti_wpack_%s_host)", bits,
+                        (bits & TI_BITS_KQ) ? "Q4_K" : "MXFP4", (bits & TI_BITS_KQ) ? "kq" : "mx");
   bits &= ~TI_BITS_G32;
   if (!q || !d || !tiles || !scales) return ti_set_error(TI_ERR_ARG, "ti_wpack_q_host: null pointer");
   if (bits != 4 && bits != 8) return ti_set_error(TI_ERR_ARG, "ti_wpack_q_host: bits %d (4 or 8)", bits);
@@ -163,6 +206,9 @@ extern "C" int ti_wpack_q_host(const int8_t* q, const uint16_t* d, int K, int N_
 extern "C" int ti_wpack_host(const float* w, int K, int N_src, int N_total, int bits, int scale_mode, int row_map,
                              int row_offset, void* tiles, uint16_t* scales) {
   if (!w || !tiles) return ti_set_error(TI_ERR_ARG, "ti_wpack_host: null pointer");
+  if (bits & TI_BITS_KQ)
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_wpack_host: TI_BITS_KQ (Q4_K super-blocks) takes exact blocks "
+                        "(ti_wpack_kq_host), not fp32 values");
   if (bits == (4 | TI_BITS_G32 | TI_BITS_AFF)) {
     // fp32 weights onto an affine group-32 engine: ggml's Q4_1 rounding per 32-block
     // (d = (max - min) / 15, m = min, q = round-half-up((w - min) / d) clamped to 15), then packed exactly

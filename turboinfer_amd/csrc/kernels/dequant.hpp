@@ -60,6 +60,19 @@ __device__ __forceinline__ f16x8 deq_mxfp4(uint32_t w) {
 // The e8m0 block scale as fp32: 2^(e - 127) for 1 <= e <= 254.
 __device__ __forceinline__ float e8m0_to_f32(uint32_t e) { return __builtin_bit_cast(float, e << 23); }
 
+// Q4_K (TI_BITS_KQ): the same word layout with the raw q (0..15) per nibble, widened exactly: (w & 0x000F000F) |
+// 0x64006400 is fp16 1024 + q and (w & 0x00F000F0) | 0x54005400 is fp16 64 + q (one ulp at 64 is 1/16, the nibble
+// sits 4 bits up); a packed subtract of 1024 / 64 leaves q (gemm_w4a.hip's deq_q4_exact without the offset 8).
+__device__ __forceinline__ f16x8 deq_q4k(uint32_t w) {
+  const f16x2 k1024 = {(f16)1024.0f, (f16)1024.0f}, k64 = {(f16)64.0f, (f16)64.0f};
+  const uint32_t w8 = w >> 8;
+  const f16x2 e01 = __builtin_bit_cast(f16x2, (w & 0x000F000Fu) | 0x64006400u) - k1024;
+  const f16x2 e23 = __builtin_bit_cast(f16x2, (w & 0x00F000F0u) | 0x54005400u) - k64;
+  const f16x2 e45 = __builtin_bit_cast(f16x2, (w8 & 0x000F000Fu) | 0x64006400u) - k1024;
+  const f16x2 e67 = __builtin_bit_cast(f16x2, (w8 & 0x00F000F0u) | 0x54005400u) - k64;
+  return (f16x8){e01[0], e01[1], e23[0], e23[1], e45[0], e45[1], e67[0], e67[1]};
+}
+
 template <int BITS>
 __device__ __forceinline__ f16x8 dequant_step(const u32x4 (&w)[BITS / 4], int s4, uint32_t magic) {
   if constexpr (BITS == 4) {

@@ -98,15 +98,17 @@ __host__ inline const GemmKnobs& gemm_knobs() {
 // Workgroups per launch: one 8-wave workgroup per CU (a second workgroup per CU measured slower,
 // DESIGN 4.1), never more than there are 16-row tiles.
 
-__host__ __device__ inline int gemv_lds_bytes_tiles(int M, int K, int tiles_per_wg, bool g32 = false, bool aff = false, bool mx = false);
+__host__ __device__ inline int gemv_lds_bytes_tiles(int M, int K, int tiles_per_wg, bool g32 = false, bool aff = false, bool mx = false,
+                                                    bool kq = false);
 
 // Tiles per workgroup are bounded by the LDS image (partial slabs and scales grow with
 // them): very wide outputs (a 128k vocabulary) get more workgroups than CUs.
-__host__ inline int gemv_grid(int M, int N, int K, int num_cus, bool g32 = false, bool aff = false, bool mx = false) {
+__host__ inline int gemv_grid(int M, int N, int K, int num_cus, bool g32 = false, bool aff = false, bool mx = false,
+                              bool kq = false) {
   const int NT = N >> 4;
   const int g = num_cus > 0 ? num_cus : 256;
   int grid = NT < g ? NT : g;
-  while (grid < NT && gemv_lds_bytes_tiles(M, K, (NT + grid - 1) / grid, g32, aff, mx) > 160 * 1024) grid += grid / 8 + 1;
+  while (grid < NT && gemv_lds_bytes_tiles(M, K, (NT + grid - 1) / grid, g32, aff, mx, kq) > 160 * 1024) grid += grid / 8 + 1;
   return grid < NT ? grid : NT;
 }
 
@@ -121,6 +123,7 @@ __host__ inline int gemv_grid(int M, int N, int K, int num_cus, bool g32 = false
 //          outputs, TI_EPI_RESID_F32 with fold_x), or RoPE (cos, sin) [M][hd] + pos [M]
 //   best   [16] u64                   argmax keys of the workgroup
 //   (MXFP4, TI_BITS_MX: scales [ntl][K/128][4][16] e8m0 bytes, no corr)
+//   (Q4_K, TI_BITS_KQ: gemv_lds_layout_kq below)
 //   (affine group-32, TI_BITS_AFF: + the block minimums [ntl][K/128][4][16] fp16 after the scales
 //    and the blocks' sums of x [K/32][16] f32 after corr)
 struct GemvLds {
@@ -153,7 +156,24 @@ __host__ __device__ inline GemvLds gemv_lds_layout_mx(int M, int K, int ntl) {
   l.total = l.best + 16 * 8;
   return l;
 }
-__host__ __device__ inline int gemv_lds_bytes_tiles(int M, int K, int tiles_per_wg, bool g32, bool aff, bool mx) {
+// Q4_K super-blocks (TI_BITS_KQ): x, then the decoded scale image -- per 32-block and output row the byte pair
+// (sc, m), [ntl][K/128][4][16] uint16 at sc, and per super-block and row the word d | dmin << 16, [ntl][K/256][16]
+// uint32 at mins (20 bytes per row and super-block) -- then the blocks' sums of x [K/32][16] f32; no corr table.
+__host__ __device__ inline GemvLds gemv_lds_layout_kq(int M, int K, int ntl) {
+  GemvLds l;
+  l.x = 0;
+  l.sc = l.x + align16(M * (K + 8) * 2);
+  l.mins = l.sc + ntl * (K >> 7) * 128;
+  l.corr = l.bsum = l.mins + ntl * (K >> 8) * 64;
+  l.slab = l.bsum + (K >> 5) * 16 * 4;
+  l.es = l.slab + (ntl + 1) * kGemvWaves * kWave * 16;
+  const int es_bytes = 2 * ntl * M * 16 * 4 > M * 128 * 4 + 64 ? 2 * ntl * M * 16 * 4 : M * 128 * 4 + 64;
+  l.best = l.es + align16(es_bytes);
+  l.total = l.best + 16 * 8;
+  return l;
+}
+__host__ __device__ inline int gemv_lds_bytes_tiles(int M, int K, int tiles_per_wg, bool g32, bool aff, bool mx, bool kq) {
+  if (kq) return gemv_lds_layout_kq(M, K, tiles_per_wg).total;
   return mx ? gemv_lds_layout_mx(M, K, tiles_per_wg).total : gemv_lds_layout(M, K, tiles_per_wg, g32, aff).total;
 }
 
@@ -167,8 +187,19 @@ enum { XM_F16 = 0, XM_F32 = 1, XM_NORM1 = 2, XM_NORM = 3, XM_F16F = 4, XM_ATTN =
 
 // Generic staging (M > 1 with rms_norm, f32 rows, or rows longer than the register
 // prefetch covers).  Runs after the ring is issued, so its loads wait behind the ring.
-template <int XM>
-__device__ __forceinline__ void stage_x_generic(const GemvArgs& a, f16* xl, float* red, int k8_from) {
+// The fp32 sum of one staged piece (8 fp16 values as the MFMA multiplies them), in a fixed order; Q4_K (BS): the
+// four pieces of a 32-k block sit in four adjacent lanes, whose sum goes to bsum[block][row].
+__device__ __forceinline__ float piece_sum(const f16x8& h) {
+  return (((float)h[0] + (float)h[1]) + ((float)h[2] + (float)h[3])) + (((float)h[4] + (float)h[5]) + ((float)h[6] + (float)h[7]));
+}
+__device__ __forceinline__ void put_bsum(float* bsum, const f16x8& h, int m, int k8) {
+  const float sx = group_sum<4>(piece_sum(h));
+  if ((k8 & 3) == 0) bsum[(k8 >> 2) * 16 + m] = sx;
+}
+
+template <int XM, bool BS = false>
+__device__ __forceinline__ void stage_x_generic(const GemvArgs& a, f16* xl, float* red, int k8_from,
+                                                float* bsum = nullptr) {
   const int tid = threadIdx.x, K = a.K, xs = K + 8, K8 = K >> 3;
   if constexpr (XM == XM_NORM || XM == XM_NORM1) {
     // rms_norm (tensor_engine.cpp:1488-1505): y = (x / sqrt(sum(x^2)/K + eps)) * w.
@@ -196,6 +227,7 @@ __device__ __forceinline__ void stage_x_generic(const GemvArgs& a, f16* xl, floa
         h[4] = (f16)((v1.x / rms) * w1.x); h[5] = (f16)((v1.y / rms) * w1.y);
         h[6] = (f16)((v1.z / rms) * w1.z); h[7] = (f16)((v1.w / rms) * w1.w);
         *(f16x8*)(xl + m * xs + 8 * k8) = h;
+        if constexpr (BS) put_bsum(bsum, h, m, k8);
       }
       __syncthreads();   // red reused by the next row
     }
@@ -208,11 +240,14 @@ __device__ __forceinline__ void stage_x_generic(const GemvArgs& a, f16* xl, floa
       h[0] = (f16)v0.x; h[1] = (f16)v0.y; h[2] = (f16)v0.z; h[3] = (f16)v0.w;
       h[4] = (f16)v1.x; h[5] = (f16)v1.y; h[6] = (f16)v1.z; h[7] = (f16)v1.w;
       *(f16x8*)(xl + m * xs + 8 * k8) = h;
+      if constexpr (BS) put_bsum(bsum, h, m, k8);
     }
   } else {
     for (int i = tid + k8_from; i < a.M * K8; i += kGemvThreads) {
       const int m = i / K8, k8 = i - m * K8;
-      *(u32x4*)(xl + m * xs + 8 * k8) = *(const u32x4*)((const f16*)a.x + (size_t)m * a.ldx + 8 * k8);
+      const u32x4 v = *(const u32x4*)((const f16*)a.x + (size_t)m * a.ldx + 8 * k8);
+      *(u32x4*)(xl + m * xs + 8 * k8) = v;
+      if constexpr (BS) put_bsum(bsum, __builtin_bit_cast(f16x8, v), m, k8);
     }
   }
 }
@@ -320,6 +355,21 @@ __device__ __forceinline__ float int4_x_prep(f16x8& h) {
   return 1032.0f * lo + 1152.0f * hi;
 }
 
+// One 16-byte scale entry of a Q4_K super-block (ti_hip.h) into the LDS image (gemv_lds_layout_kq).  i = (tile *
+// K/256 + super-block) * 16 + row is the entry's index in the workgroup's share of the scale buffer and also the
+// index of its d | dmin word; the eight 12-bit (sc, m) pairs come out with one shift (or v_alignbit across a word
+// boundary) each and go to [tile * K/128 + 128-k tile][block][row] as the byte pair sc | m << 8: a step then
+// reads 16 rows' pairs from 8 consecutive banks and the item's d | dmin words from 16, the four lanes of a row the
+// same address.
+__device__ __forceinline__ void kq_stage_entry(const u32x4 v, int i, uint16_t* sl, uint32_t* dd) {
+  dd[i] = v[0];
+  const uint32_t pr[8] = {v[1], v[1] >> 12, __builtin_amdgcn_alignbit(v[2], v[1], 24), v[2] >> 4,
+                          v[2] >> 16, __builtin_amdgcn_alignbit(v[3], v[2], 28), v[3] >> 8, v[3] >> 20};
+  uint16_t* p = sl + (i >> 4) * 128 + (i & 15);   // (two 128-k tiles of 4 blocks x 16 rows per super-block)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) p[j * 16] = (uint16_t)((pr[j] & 63u) | ((pr[j] << 2) & 0x3f00u));
+}
+
 // --------------------------------------------------------------------- kernel
 
 // The fields on the prologue's critical path come first as separate arguments: gfx950 can
@@ -342,12 +392,13 @@ __device__ __forceinline__ float int4_x_prep(f16x8& h) {
 // EPI >= 0: the one-row instance of one epilogue kind (M == 1, at most one output per thread: see the
 // one-row tail behind the stream and onerow_epi() in launch_gemv); -1: the generic body.
 // The body is gemv_wq_body.inc, included into the two entry points below (gemv_wq_kernel, gemv_mx_kernel).
+// KQ: Q4_K super-blocks (TI_BITS_KQ) on the group-32 int4 tiles: see gemv_kq_kernel below.
 template <int BITS, int XM, bool G32 = false, bool AFF = false, int EPI = -1>
 __global__ __launch_bounds__(kGemvThreads, 1) void gemv_wq_kernel(const u32x4* p_tiles, const uint16_t* p_scales,
                                                                    const void* p_x, const float* p_aux, int p_mgk,
                                                                    int p_N, int p_kx, int p_ldo, const float* p_pre,
                                                                    GemvArgs a) {
-  constexpr bool MX = false;
+  constexpr bool MX = false, KQ = false;
 #include "gemv_wq_body.inc"
 }
 
@@ -360,7 +411,7 @@ __device__ __forceinline__ void gemv_mx_body(const u32x4* p_tiles, const uint16_
                                              const float* p_aux, int p_mgk, int p_N, int p_kx, int p_ldo,
                                              const float* p_pre, GemvArgs a) {
   constexpr int BITS = 4;
-  constexpr bool G32 = true, AFF = false, MX = true;
+  constexpr bool G32 = true, AFF = false, MX = true, KQ = false;
 #include "gemv_wq_body.inc"
 }
 template <int XM, int EPI = -1>
@@ -368,6 +419,29 @@ __global__ __launch_bounds__(kGemvThreads, 1) __attribute__((target("no-packed-f
     const u32x4* p_tiles, const uint16_t* p_scales, const void* p_x, const float* p_aux, int p_mgk, int p_N, int p_kx,
     int p_ldo, const float* p_pre, GemvArgs a) {
   gemv_mx_body<XM, EPI>(p_tiles, p_scales, p_x, p_aux, p_mgk, p_N, p_kx, p_ldo, p_pre, a);
+}
+
+// The Q4_K entry point (TI_BITS_KQ): the same body text with KQ set, built like the MX one (scalar fp32 FMAs, the
+// body in a __forceinline__ function).  What is its own in the body:
+//   * scale staging: the thread that prefetched a 16-byte entry decodes it into LDS (kq_stage_entry) while the
+//     weight ring is in flight; the image keeps the 6-bit fields as bytes and d, dmin as halves;
+//   * x is used as staged; where a piece of x is staged, its fp32 sum is taken from the fp16 values the MFMA
+//     multiplies and four adjacent lanes' sums make bsum[block][row] (no pass over x behind the staging barrier);
+//   * the step: nibbles widened exactly (deq_q4k), one MFMA per 32-block from zero, then per output
+//     acc = fmaf(float(d) * sc, sum, acc); acc = fmaf(-float(dmin) * m, sx, acc), in k order.
+template <int XM, int EPI>
+__device__ __forceinline__ void gemv_kq_body(const u32x4* p_tiles, const uint16_t* p_scales, const void* p_x,
+                                             const float* p_aux, int p_mgk, int p_N, int p_kx, int p_ldo,
+                                             const float* p_pre, GemvArgs a) {
+  constexpr int BITS = 4;
+  constexpr bool G32 = true, AFF = false, MX = false, KQ = true;
+#include "gemv_wq_body.inc"
+}
+template <int XM, int EPI = -1>
+__global__ __launch_bounds__(kGemvThreads, 1) __attribute__((target("no-packed-fp32-ops"))) void gemv_kq_kernel(
+    const u32x4* p_tiles, const uint16_t* p_scales, const void* p_x, const float* p_aux, int p_mgk, int p_N, int p_kx,
+    int p_ldo, const float* p_pre, GemvArgs a) {
+  gemv_kq_body<XM, EPI>(p_tiles, p_scales, p_x, p_aux, p_mgk, p_N, p_kx, p_ldo, p_pre, a);
 }
 
 // ================================================================= batched rows
@@ -1672,7 +1746,7 @@ __host__ inline bool onerow_epi(const GemvArgs& a, int xm, int grid) {
   return true;
 }
 
-template <int BITS, bool G32 = false, bool AFF = false, bool MX = false>
+template <int BITS, bool G32 = false, bool AFF = false, bool MX = false, bool KQ = false>
 static int launch_gemv(const GemvArgs& a, int lds, hipStream_t s, int grid) {
   const float* pre = a.epi.kind == TI_EPI_RESID_F32 ? (const float*)a.epi.out
                      : a.epi.kind == TI_EPI_QKV_ROPE_KV ? (const float*)a.epi.pos : (const float*)a.x;
@@ -1686,6 +1760,31 @@ static int launch_gemv(const GemvArgs& a, int lds, hipStream_t s, int grid) {
   if (nt_q > 255 || nt_r >= (1 << 23))
     return ti_set_error(TI_ERR_UNSUPPORTED, "gemv_wq_kernel: %d tiles over %d workgroups", NT, grid);
   const int pn = nt_q | (nt_r << 8);
+  if constexpr (KQ) {   // gemv_kq_kernel: the one-row instances the MX entry point has, then the generic ones
+#define TI_KQ_LAUNCH(...)                                                                                        \
+  hipLaunchKernelGGL((gemv_kq_kernel<__VA_ARGS__>), dim3(grid), dim3(kGemvThreads), lds, s, a.tiles, a.scales, a.x, aux, \
+                     mgk, pn, kx, ldo, pre, a)
+    bool onerow = onerow_epi(a, xm, grid);
+    if (onerow && xm == XM_ATTN && a.epi.kind == TI_EPI_RESID_F32) TI_KQ_LAUNCH(XM_ATTN, TI_EPI_RESID_F32);
+    else if (onerow && xm == XM_F16 && a.epi.kind == TI_EPI_RESID_F32) TI_KQ_LAUNCH(XM_F16, TI_EPI_RESID_F32);
+    else if (onerow && xm == XM_NORM1 && a.epi.kind == TI_EPI_SILU_MUL_F16) TI_KQ_LAUNCH(XM_NORM1, TI_EPI_SILU_MUL_F16);
+    else if (onerow && xm == XM_NORM1 && a.epi.kind == TI_EPI_LOGITS_ARGMAX) TI_KQ_LAUNCH(XM_NORM1, TI_EPI_LOGITS_ARGMAX);
+    else if (onerow && xm == XM_NORM1 && a.epi.kind == TI_EPI_QKV_ROPE_KV) TI_KQ_LAUNCH(XM_NORM1, TI_EPI_QKV_ROPE_KV);
+    else {
+      onerow = false;
+      switch (xm) {
+        case XM_F16: TI_KQ_LAUNCH(XM_F16); break;
+        case XM_F32: TI_KQ_LAUNCH(XM_F32); break;
+        case XM_ATTN: TI_KQ_LAUNCH(XM_ATTN); break;
+        case XM_NORM1: TI_KQ_LAUNCH(XM_NORM1); break;
+        default: TI_KQ_LAUNCH(XM_NORM); break;
+      }
+    }
+#undef TI_KQ_LAUNCH
+    TI_LAUNCH_CHECK("gemv_kq_kernel");
+    if (onerow) g_onerow_epi_launches.fetch_add(1, std::memory_order_relaxed);
+    return TI_OK;
+  }
   if constexpr (BITS != 16 && (!G32 || MX) && !AFF) {
     // one-row instances (gemv_wq_kernel EPI >= 0); anything else falls through to the generic ones
 #define TI_ONEROW(XMODE, KIND)                                                                                  \
@@ -1971,6 +2070,11 @@ extern "C" int ti_gemm_prepare(void) {
       (const void*)gemv_mx_kernel<XM_ATTN, TI_EPI_RESID_F32>,
       (const void*)gemv_mx_kernel<XM_F16, TI_EPI_RESID_F32>, (const void*)gemv_mx_kernel<XM_NORM1, TI_EPI_SILU_MUL_F16>,
       (const void*)gemv_mx_kernel<XM_NORM1, TI_EPI_LOGITS_ARGMAX>, (const void*)gemv_mx_kernel<XM_NORM1, TI_EPI_QKV_ROPE_KV>,
+      (const void*)gemv_kq_kernel<XM_F16>, (const void*)gemv_kq_kernel<XM_F32>, (const void*)gemv_kq_kernel<XM_NORM1>,
+      (const void*)gemv_kq_kernel<XM_NORM>, (const void*)gemv_kq_kernel<XM_ATTN>,
+      (const void*)gemv_kq_kernel<XM_ATTN, TI_EPI_RESID_F32>,
+      (const void*)gemv_kq_kernel<XM_F16, TI_EPI_RESID_F32>, (const void*)gemv_kq_kernel<XM_NORM1, TI_EPI_SILU_MUL_F16>,
+      (const void*)gemv_kq_kernel<XM_NORM1, TI_EPI_LOGITS_ARGMAX>, (const void*)gemv_kq_kernel<XM_NORM1, TI_EPI_QKV_ROPE_KV>,
       TI_MB_FNS, TI_ROWS_FNS, TI_TILE_FNS};
   for (const void* f : fns)
     TI_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
@@ -1994,10 +2098,10 @@ extern "C" int ti_gemm_lds_bytes(int M, int N, int K) {
 // int4 with more than 2 rows goes to the batched-rows kernel: from 4 rows on it is faster at
 // every 7B projection (bench.py --batch 2..16, rocprof), at 2 rows the two tie.
 static int fused_rows_pref(int bits) { return bits == 4 ? 2 : 16; }
-static bool fused_fits(int M, int N, int K, bool g32 = false, bool aff = false, bool mx = false) {
+static bool fused_fits(int M, int N, int K, bool g32 = false, bool aff = false, bool mx = false, bool kq = false) {
   if (M > 16) return false;
-  const int NT = N >> 4, grid = ti::gemv_grid(M, N, K, query_cus(), g32, aff, mx);
-  return ti::gemv_lds_bytes_tiles(M, K, (NT + grid - 1) / grid, g32, aff, mx) <= 160 * 1024;
+  const int NT = N >> 4, grid = ti::gemv_grid(M, N, K, query_cus(), g32, aff, mx, kq);
+  return ti::gemv_lds_bytes_tiles(M, K, (NT + grid - 1) / grid, g32, aff, mx, kq) <= 160 * 1024;
 }
 static bool use_batched(int bits, int x_kind, int M, int N, int K) {
   const bool mb_ok = bits == 4 && x_kind == TI_X_F16;
@@ -2132,15 +2236,17 @@ extern "C" int ti_gemm_tile_plan(int bits, int M, int N, int K, int64_t ws_bytes
 }
 
 extern "C" int ti_gemm_max_rows(int bits, int x_kind, int N, int K) {
-  if (N < 16 || K < 128 || ((bits & TI_BITS_MX) && !(bits & TI_BITS_G32))) return 0;
+  if (N < 16 || K < 128 || ((bits & (TI_BITS_MX | TI_BITS_KQ)) && !(bits & TI_BITS_G32))) return 0;
   if (bits & TI_BITS_G32) {   // group-32 weights: the fused kernel; int4 fp16 rows also the tile kernel
     const bool aff = (bits & TI_BITS_AFF) != 0;   // (affine blocks: fused pieces only)
     const bool mx = (bits & TI_BITS_MX) != 0;     // (MXFP4 blocks: fused pieces only)
+    const bool kq = (bits & TI_BITS_KQ) != 0;     // (Q4_K super-blocks: fused pieces only)
     if (x_kind == TI_X_F16_PACKED || (mx && bits != (4 | TI_BITS_G32 | TI_BITS_MX))) return 0;
-    if ((bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX)) == 4 && x_kind == TI_X_F16) return TI_GEMM_MAX_ROWS;   // 16-row pieces
+    if (kq && (bits != (4 | TI_BITS_G32 | TI_BITS_KQ) || (K & 255) || x_kind == TI_X_F16_FOLDED)) return 0;
+    if ((bits & ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX | TI_BITS_KQ)) == 4 && x_kind == TI_X_F16) return TI_GEMM_MAX_ROWS;   // 16-row pieces
     int m = 16;
-    while (m > 1 && !fused_fits(m, N, K, true, aff, mx)) --m;
-    return fused_fits(m, N, K, true, aff, mx) ? m : 0;
+    while (m > 1 && !fused_fits(m, N, K, true, aff, mx, kq)) --m;
+    return fused_fits(m, N, K, true, aff, mx, kq) ? m : 0;
   }
   if (bits == 4 && (x_kind == TI_X_F16 || x_kind == TI_X_F16_PACKED)) return TI_GEMM_MAX_ROWS;
   if (x_kind == TI_X_F16_PACKED) return 0;
@@ -2179,23 +2285,26 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
   using namespace ti;
   if (!tiles || !x || !epi || !epi->out) return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: null pointer");
   const bool g32 = (bits & TI_BITS_G32) != 0, aff = (bits & TI_BITS_AFF) != 0, mx = (bits & TI_BITS_MX) != 0;
-  bits &= ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX);
+  const bool kq = (bits & TI_BITS_KQ) != 0;
+  bits &= ~(TI_BITS_G32 | TI_BITS_AFF | TI_BITS_MX | TI_BITS_KQ);
   if ((bits != 4 && bits != 8 && bits != 16) || (g32 && bits == 16) || (aff && (!g32 || bits != 4)) ||
-      (mx && (!g32 || aff || bits != 4)))
-    return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: bits must be 4, 8 or 16 (+ TI_BITS_G32 for 4 / 8, + TI_BITS_AFF "
-                        "or TI_BITS_MX for 4 | G32; got %d)", bits);
+      (mx && (!g32 || aff || bits != 4)) || (kq && (!g32 || aff || mx || bits != 4)))
+    return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: bits must be 4, 8 or 16 (+ TI_BITS_G32 for 4 / 8, + TI_BITS_AFF, "
+                        "TI_BITS_MX or TI_BITS_KQ for 4 | G32; got %d)", bits);
+  if (kq && (K & 255))
+    return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: Q4_K super-blocks (TI_BITS_KQ) need K %% 256 == 0 (K=%d)", K);
   // group-32: int4 fp16 rows from tile_rows() on run on the tile kernel, everything else on the
   // fused kernel (more than 16 rows: in 16-row pieces, below); affine blocks on the fused kernel and, fp16 rows
   // above 16, on gemm_w4a_kernel (g32_w4a below); MXFP4 blocks the same way on gemm_mx_kernel (g32_mx) once its
   // switch is on
-  const bool g32_tile = g32 && !aff && !mx && bits == 4 && x_kind == TI_X_F16 && M >= tile_rows() && !epi->out_packed;
+  const bool g32_tile = g32 && !aff && !mx && !kq && bits == 4 && x_kind == TI_X_F16 && M >= tile_rows() && !epi->out_packed;
   // group-32 int4 fp16 rows 17..64: the batched-rows kernel (TI_GEMM_G32_ROWS=0: fused pieces, A/B knob)
-  const bool g32_rowsk = g32 && !aff && !mx && bits == 4 && x_kind == TI_X_F16 && M > 16 && M < tile_rows() &&
+  const bool g32_rowsk = g32 && !aff && !mx && !kq && bits == 4 && x_kind == TI_X_F16 && M > 16 && M < tile_rows() &&
                          !epi->out_packed && g32_rows_on();
   int g32_rows = 16;   // rows per fused launch (its LDS image holds the x rows)
-  while (g32 && g32_rows > 1 && !fused_fits(g32_rows, N, K, true, aff, mx)) --g32_rows;
+  while (g32 && g32_rows > 1 && !fused_fits(g32_rows, N, K, true, aff, mx, kq)) --g32_rows;
   if (g32 && (x_kind == TI_X_F16_PACKED ||
-              (!g32_tile && !g32_rowsk && !fused_fits(std::min(M, g32_rows), N, K, true, aff, mx))))
+              (!g32_tile && !g32_rowsk && !fused_fits(std::min(M, g32_rows), N, K, true, aff, mx, kq))))
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: group-32 weights: fused kernel rows (M=%d N=%d K=%d) "
                         "or int4 fp16 rows >= %d; no packed rows", M, N, K, tile_rows());
   if (bits != 16 && !scales) return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: scales required for bits %d", bits);
@@ -2215,9 +2324,9 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
   if (x_kind == TI_X_F16_FOLDED && (M != 1 || !epi->ss_in || epi->n_ss < 1 || epi->n_ss > 256))
     return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: TI_X_F16_FOLDED needs M == 1, ss_in and 1 <= n_ss <= 256");
   const bool fold_out = epi->kind == TI_EPI_RESID_F32 && epi->fold_x;
-  if (mx && (x_kind == TI_X_F16_FOLDED || fold_out))
-    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: MXFP4 weights take no folded rms_norm hand-off "
-                        "(TI_X_F16_FOLDED input, fold_x output)");
+  if ((mx || kq) && (x_kind == TI_X_F16_FOLDED || fold_out))
+    return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: %s weights take no folded rms_norm hand-off "
+                        "(TI_X_F16_FOLDED input, fold_x output)", kq ? "Q4_K (TI_BITS_KQ)" : "MXFP4");
   if (fold_out && M == 1 && (!epi->fold_w || !epi->fold_ss || (x_kind != TI_X_F16 && x_kind != TI_X_ATTN_SPLITS)))
     return ti_set_error(TI_ERR_ARG, "ti_gemm_wq_a16: fold_x needs M == 1, fp16 x, fold_w and fold_ss");
   if (fold_out && M > 1 && (!epi->fold_w || !epi->fold_ss || x_kind != TI_X_F16_PACKED || M > TI_FOLD_SS_ROWS ||
@@ -2282,7 +2391,7 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
       if (ep.v_cache) ep.v_cache = (uint16_t*)((char*)ep.v_cache + (size_t)m0 * ep.kv_stream_stride * kv_esz);
       if (ep.argmax) ep.argmax += (size_t)m0 * TI_ARGMAX_SLOTS;
       if (m0 + mm < M) ep.step_ctr = nullptr;
-      const int rc = gemm_impl(tiles, scales, bits | TI_BITS_G32 | (aff ? TI_BITS_AFF : 0) | (mx ? TI_BITS_MX : 0),
+      const int rc = gemm_impl(tiles, scales, bits | TI_BITS_G32 | (aff ? TI_BITS_AFF : 0) | (mx ? TI_BITS_MX : 0) | (kq ? TI_BITS_KQ : 0),
                                static_cast<const char*>(x) + (size_t)m0 * ldx * x_elem,
                                x_kind, ldx, norm_w, eps, mm, N, K, &ep, stream);
       if (rc != TI_OK) return rc;
@@ -2419,8 +2528,8 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
     grid = mb_grid(MB, N, K, query_cus(), &ntl);
     lds = mb_use_lds(MB) ? mb_lds_bytes(MB, ntl, K) : mbr_lds_bytes(MB, ntl, K);
   } else {
-    grid = gemv_grid(M, N, K, query_cus(), g32, aff, mx);
-    lds = gemv_lds_bytes_tiles(M, K, ((N >> 4) + grid - 1) / grid, g32, aff, mx);
+    grid = gemv_grid(M, N, K, query_cus(), g32, aff, mx, kq);
+    lds = gemv_lds_bytes_tiles(M, K, ((N >> 4) + grid - 1) / grid, g32, aff, mx, kq);
   }
   if ((fold_out && M > 1 && !rows) || (fold_in && !rows && !tile))
     return ti_set_error(TI_ERR_UNSUPPORTED, "ti_gemm_wq_a16: the batched fold runs on the batched-rows (fold_x) / "
@@ -2461,6 +2570,7 @@ static int gemm_impl(const void* tiles, const uint16_t* scales, int bits, const 
   if (batched) return launch_mb(a, M > 16 ? 2 : 1, grid, ntl, lds, s);
   if (aff) return launch_gemv<4, true, true>(a, lds, s, grid);
   if (mx) return launch_gemv<4, true, false, true>(a, lds, s, grid);
+  if (kq) return launch_gemv<4, true, false, false, true>(a, lds, s, grid);
   if (g32) return bits == 4 ? launch_gemv<4, true>(a, lds, s, grid) : launch_gemv<8, true>(a, lds, s, grid);
   if (bits == 4) return launch_gemv<4>(a, lds, s, grid);
   if (bits == 8) return launch_gemv<8>(a, lds, s, grid);
@@ -2476,9 +2586,9 @@ extern "C" int ti_epilogue_bytes(void) { return (int)sizeof(ti_epilogue); }
 extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, char* buf, int len) {
   using namespace ti;
   const bool q8_0 = bits == (8 | TI_BITS_G32), q4_1 = bits == (4 | TI_BITS_G32 | TI_BITS_AFF);
-  const bool mxfp4 = bits == (4 | TI_BITS_G32 | TI_BITS_MX);
+  const bool mxfp4 = bits == (4 | TI_BITS_G32 | TI_BITS_MX), q4_k = bits == (4 | TI_BITS_G32 | TI_BITS_KQ);
   if (!buf || len < 1) return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: null buffer");
-  if ((bits != 4 && bits != 8 && bits != 16 && !q8_0 && !q4_1 && !mxfp4) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
+  if ((bits != 4 && bits != 8 && bits != 16 && !q8_0 && !q4_1 && !mxfp4 && !q4_k) || (q4_k && (K & 255)) || M < 1 || M > TI_GEMM_MAX_ROWS || N < 16 || K < 128)
     return ti_set_error(TI_ERR_ARG, "ti_gemm_kernel_name: bits %d M %d N %d K %d", bits, M, N, K);
   if (w8_route(bits, x_kind, M)) {
     snprintf(buf, (size_t)len, "gemm_w8_kernel");
@@ -2496,6 +2606,10 @@ extern "C" int ti_gemm_kernel_name(int bits, int x_kind, int M, int N, int K, ch
   if (mxfp4) {   // gemm_mx_kernel while its switch is on, else the fused kernel's MX instance (more than 16 rows in pieces)
     if (mx_route(bits, x_kind, M)) snprintf(buf, (size_t)len, "gemm_mx_kernel");
     else snprintf(buf, (size_t)len, "gemv_mx_kernel<%d>", gemv_xmode(x_kind, M, K));
+    return TI_OK;
+  }
+  if (q4_k) {   // the fused kernel's Q4_K instance, more rows than its LDS image holds in pieces
+    snprintf(buf, (size_t)len, "gemv_kq_kernel<%d>", gemv_xmode(x_kind, M, K));
     return TI_OK;
   }
   if (q8_0) {   // the fused kernel, more than 16 rows in pieces

@@ -1,5 +1,5 @@
-// gemv_wq_body.inc -- the body of gemv_wq_kernel / gemv_mx_kernel (gemv.hip, which documents it): included inside
-// a __global__ function that has BITS, XM, G32, AFF, EPI, MX as compile-time constants and the kernel's parameters.
+// gemv_wq_body.inc -- the body of gemv_wq_kernel / gemv_mx_kernel / gemv_kq_kernel (gemv.hip, which documents it): included inside
+// a function that has BITS, XM, G32, AFF, EPI, MX, KQ as compile-time constants and the kernel's parameters.
   const unsigned long long t_entry = stamp_now();
   const unsigned bid = blockIdx.x;
   a.tiles = p_tiles;
@@ -30,9 +30,11 @@
   static_assert(!G32 || BITS != 16, "group-32 weights: int4 / int8");
   static_assert(!AFF || (G32 && BITS == 4), "affine blocks: group-32 int4");
   static_assert(!MX || (G32 && BITS == 4 && !AFF), "MXFP4 blocks: group-32 nibbles");
-  const GemvLds L = MX ? gemv_lds_layout_mx(a.M, a.K, ntl) : gemv_lds_layout(a.M, a.K, ntl, G32, AFF);
-  uint16_t* ml = (uint16_t*)(smem + L.mins);       // AFF: block minimums, as sl
-  float* bsum = (float*)(smem + L.bsum);           // AFF: [K/32][16] sums of x per block and row
+  static_assert(!KQ || (G32 && BITS == 4 && !AFF && !MX && XM != XM_F16F), "Q4_K super-blocks: group-32 nibbles");
+  const GemvLds L = KQ ? gemv_lds_layout_kq(a.M, a.K, ntl)
+                    : MX ? gemv_lds_layout_mx(a.M, a.K, ntl) : gemv_lds_layout(a.M, a.K, ntl, G32, AFF);
+  uint16_t* ml = (uint16_t*)(smem + L.mins);       // AFF: block minimums, as sl; KQ: the d | dmin words
+  float* bsum = (float*)(smem + L.bsum);           // AFF, KQ: [K/32][16] sums of x per block and row
   f16* xl = (f16*)(smem + L.x);
   uint16_t* sl = (uint16_t*)(smem + L.sc);
   float* corr = (float*)(smem + L.corr);           // [K/128][16] (int4 only)
@@ -157,7 +159,9 @@
   GEMV_TS(1);
   STAMP_MARK(ph_issued);
   // ---- 3. stage scales and x in LDS (waits only for the loads of step 1)
-  if constexpr (BITS != 16) {
+  if constexpr (KQ) {   // (entry tid of the workgroup's [ntl][K/256][16 rows]: decoded, kq_stage_entry)
+    if (tid < n_sc) kq_stage_entry(sc_reg, tid, sl, (uint32_t*)ml);
+  } else if constexpr (BITS != 16) {
     if (tid < n_sc) ((u32x4*)sl)[tid] = sc_reg;
   }
   // int4 (group 128): the x pieces staged from registers get their 1/16 scaling and offset correction
@@ -188,6 +192,7 @@
       h[6] = (f16)((v1.z / rms) * w1.z); h[7] = (f16)((v1.w / rms) * w1.w);
       if constexpr (kRegPrep) part = int4_x_prep(h);
       *(f16x8*)(xl + 8 * tid) = h;
+      if constexpr (KQ) put_bsum(bsum, h, 0, tid);
     }
     if constexpr (kRegPrep) {
       part = group_sum<16>(part);
@@ -216,6 +221,7 @@
       for (int e = 0; e < 8; ++e) hx[e] = (f16)(den > 0.0f ? num[e] / den : 0.0f);
       if constexpr (kRegPrep) part = int4_x_prep(hx);
       *(f16x8*)(xl + 8 * tid) = hx;
+      if constexpr (KQ) put_bsum(bsum, hx, 0, tid);
     }
     if constexpr (kRegPrep) {
       part = group_sum<16>(part);
@@ -234,6 +240,7 @@
           *(f16x8*)(xl + m * xs + 8 * k8) = h;
         } else {
           *(u32x4*)(xl + m * xs + 8 * k8) = xr16[q];
+          if constexpr (KQ) put_bsum(bsum, __builtin_bit_cast(f16x8, xr16[q]), m, k8);
         }
       }
       if (kRegPrep && reg_prep) {   // (uniform: every lane of a 16-lane group has the same q)
@@ -243,7 +250,9 @@
     }
   }
   // rare shapes: what the register prefetch did not cover (these loads wait behind the ring)
-  if constexpr (BITS != 16) {
+  if constexpr (KQ) {
+    for (int i = tid + kGemvThreads; i < n_sc; i += kGemvThreads) kq_stage_entry(sg[i], i, sl, (uint32_t*)ml);
+  } else if constexpr (BITS != 16) {
     for (int i = tid + kGemvThreads; i < n_sc; i += kGemvThreads) ((u32x4*)sl)[i] = sg[i];
   }
   if constexpr (AFF) {   // the minimums follow all N/16 tiles' scales in the same buffer
@@ -251,9 +260,9 @@
     for (int i = tid; i < n_sc; i += kGemvThreads) ((u32x4*)ml)[i] = mg[i];
   }
   if constexpr (XM == XM_F16 || XM == XM_F16F) {
-    if (nx16 > XPF * kGemvThreads) stage_x_generic<XM>(a, xl, red, XPF * kGemvThreads);
+    if (nx16 > XPF * kGemvThreads) stage_x_generic<XM, KQ>(a, xl, red, XPF * kGemvThreads, bsum);
   } else if constexpr (XM != XM_NORM1 && XM != XM_ATTN) {
-    stage_x_generic<XM>(a, xl, red, 0);
+    stage_x_generic<XM, KQ>(a, xl, red, 0, bsum);
   }
   if ((EPI >= 0 ? kind : a.epi.kind) == TI_EPI_QKV_ROPE_KV && tid < a.M) ((int*)(es + a.M * a.epi.head_dim))[tid] = __builtin_bit_cast(int, pre);
   if (tid < 16) best_l[tid] = 0ull;
@@ -265,7 +274,7 @@
 #pragma unroll
     for (int c = 0; c < C; ++c) ring[s][c] = ld_w(tb + o + c * kWave);
   }
-  if constexpr (BITS == 4 && !MX) if (!reg_prep) {
+  if constexpr (BITS == 4 && !MX && !KQ) if (!reg_prep) {
     // Offset-folded int4 (deq_int4_raw): scale the high-nibble slots of x by 1/16 (exact in
     // fp16) and build corr[g][m] = 1032 * sum_lo a + 1152 * sum_hi a per 128-k group.  A
     // group is 16 consecutive k8 pieces, i.e. 16 consecutive lanes (K8 % 16 == 0).
@@ -369,7 +378,28 @@
     const int kt = wave + kGemvWaves * ck;
     f32x4 t = {0.0f, 0.0f, 0.0f, 0.0f};
     if constexpr (BITS == 16) t = acc;
-    if constexpr (G32) {
+    if constexpr (KQ) {
+      const f16* xr32 = xrow - kq * 32 + kq * 8;   // this lane's 8 k of each 32-k block
+      const uint32_t ddw = ((const uint32_t*)ml)[(ct * (KT >> 1) + (kt >> 1)) * 16 + r];   // the super-block's d | dmin
+      const float fd = h2f((uint16_t)ddw), fnm = -h2f((uint16_t)(ddw >> 16));
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        const f16x8 bf = deq_q4k(w[0][s4]);
+        const f16x8 af = *(const f16x8*)(xr32 + kt * 128 + s4 * 32);
+        const f32x4 tb = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, (f32x4){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+        const uint32_t scm = sl[((ct * KT + kt) * 4 + s4) * 16 + r];   // sc | m << 8 of the block
+        const float dsc = fd * (float)(scm & 0xffu), nm = fnm * (float)(scm >> 8);   // (both exact in fp32)
+        const f32x4 bs = *(const f32x4*)(bsum + (kt * 4 + s4) * 16 + 4 * kq);
+        acc[0] = fmaf(dsc, tb[0], acc[0]);
+        acc[1] = fmaf(dsc, tb[1], acc[1]);
+        acc[2] = fmaf(dsc, tb[2], acc[2]);
+        acc[3] = fmaf(dsc, tb[3], acc[3]);
+        acc[0] = fmaf(nm, bs[0], acc[0]);
+        acc[1] = fmaf(nm, bs[1], acc[1]);
+        acc[2] = fmaf(nm, bs[2], acc[2]);
+        acc[3] = fmaf(nm, bs[3], acc[3]);
+      }
+    } else if constexpr (G32) {
       const f16* xr32 = xrow - kq * 32 + kq * 8;   // this lane's 8 k of each 32-k block
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) {
@@ -420,7 +450,7 @@
       acc[2] = fmaf(sc, t[2], acc[2]);
       acc[3] = fmaf(sc, t[3], acc[3]);
     }
-    }   // !G32
+    }   // !KQ && !G32
     // the tile's last item lands in its slab, every other item in the dummy slab
     const bool last = ++ck == KW;
     my_slab[(last ? ct : ntl) * kSlabStride] = acc;

@@ -131,6 +131,8 @@ __device__ __forceinline__ void step_begin_body(const ti_step_args a) {
 // ---------------------------------------------------------- synthetic weights
 int launch_wsynth_mx(uint64_t stream_id, int K, int N_src, int row_map, int row_offset, float amp, void* tiles,
                      void* scales, hipStream_t s);   // wsynth_mx.hip
+int launch_wsynth_kq(uint64_t stream_id, int K, int N_src, int row_map, int row_offset, float amp, void* tiles,
+                     void* scales, hipStream_t s);   // wsynth_kq.hip
 __host__ __device__ inline int map_row(int c, int row_map, int row_offset) {
   return row_map == TI_ROWS_INTERLEAVE8 ? 16 * (c >> 3) + (c & 7) + row_offset : row_offset + c;
 }
@@ -308,6 +310,11 @@ extern "C" int ti_wsynth_device(uint64_t seed, uint32_t tensor_id, int K, int N_
   if (!scales) return ti_set_error(TI_ERR_ARG, "ti_wsynth_device: scales required");
   if (bits == (4 | TI_BITS_G32 | TI_BITS_MX))   // MXFP4 blocks: wsynth_mx.hip
     return launch_wsynth_mx(stream_id, K, N_src, row_map, row_offset, amp, tiles, scales, s);
+  if (bits == (4 | TI_BITS_G32 | TI_BITS_KQ)) {   // Q4_K super-blocks (seeded random blocks): wsynth_kq.hip
+    if ((K & 255) || ((uintptr_t)scales & 15))
+      return ti_set_error(TI_ERR_ARG, "ti_wsynth_device: TI_BITS_KQ needs K %% 256 == 0 and 16-byte aligned scales (K=%d)", K);
+    return launch_wsynth_kq(stream_id, K, N_src, row_map, row_offset, amp, tiles, scales, s);
+  }
   const int64_t n = (int64_t)N_src * (K >> 7);
   const dim3 grid((unsigned)((n + 127) / 128));
   if (bits == 4)
